@@ -8,6 +8,8 @@ itself, run for exactly K iterations.  Model generation, Iter0 and the W warmup
 iterations are outside it.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scens S] [--cm CM]
+    python bench.py --full                            # + CPU baseline and oracle self-check
+    python bench.py --dump-outputs DIR                # + the last timed step's PH state as .npy
     python bench.py --model aircond --bf 32,32,64     # config 4 (multistage)
     python bench.py --model uc [--scens 1000]          # config 5 (UC LP relaxation, path 4)
 
@@ -16,6 +18,12 @@ iterations are outside it.
 rehearsal on a 1-GPU box; the x̄ all-reduce then goes through host memory).  Scenarios
 are sharded contiguously (sputils.py:798-810); the total is fixed (strong scaling).
 Rank 0 prints ONE JSON line on stdout (everything else goes to stderr).
+
+A plain run sets up, warms up, times the K steps and prints the line.  ``--full`` adds
+what the headline figure does not need: the CPU baseline of the workload and the
+self-check of the warmup against the oracle fixture (``--check``).  ``--dump-outputs DIR``
+writes what the timed loop leaves its caller after its last step (W, x̄, the nonant
+values, the scenario objectives, conv) as DIR/<name>.npy (float64, rank 0's scenarios).
 """
 import argparse
 import contextlib
@@ -67,18 +75,30 @@ def parse():
     p.add_argument("--default-solver-options", action="store_true",
                    help="farmer: ignore the example's recommended PH-solve options (library defaults)")
     p.add_argument("--check", choices=["auto", "on", "off"], default="auto",
-                   help="compare the warmup with the oracle fixture of the workload (farmer 65,536 cm=1, "
+                   help="--full: compare the warmup with the oracle fixture of the workload (farmer 65,536 cm=1, "
                         "farmer 1,024 cm=10, aircond 32x32x64) and exit non-zero on a mismatch; auto: when "
                         "the workload and rho match a fixture, on: whenever the workload has one (a "
                         "different --rho then fails by design)")
     p.add_argument("--fused-loop", action="store_true",
                    help="one rank: PHBase.iterk_loop's K iterations in one cooperative launch (phgpu_ph_loop, "
                         "opt-in: measured no faster than the step-by-step loop, DESIGN.md 3.11)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also what the headline figure does not need: the CPU baseline and the self-check "
+                        "of the warmup against the oracle fixture (--check)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write the PH state the timed loop left (W, xbar, nonants, "
+                        "obj, conv; rank 0's scenarios) as DIR/<name>.npy, float64, at most 64 MB in all")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU baseline")
     p.add_argument("--cpu-sample", type=int, default=0, help="scenarios in the CPU sample (0 = auto)")
     p.add_argument("--profile-dir", default=None,
                    help="profiles/<round> directory holding the PMC summaries (default: newest)")
-    return p.parse_args()
+    a = p.parse_args()
+    if not a.full:
+        if a.check == "on":
+            p.error("--check on needs --full (a plain run does not compare with the fixture)")
+        a.check = "off"
+        a.no_cpu_baseline = True
+    return a
 
 
 def log(*a):
@@ -541,6 +561,33 @@ def combine_checks(per_rank, world_size, backend):
     return out
 
 
+# ---------------------------------------------------------------- output dump
+DUMP_BUDGET = 64_000_000  # bytes over all arrays of one --dump-outputs
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, arrays):
+    """Write ``arrays`` ({name: array}) as out_dir/<name>.npy in float64.  When they exceed
+    DUMP_BUDGET together, an array larger than an equal share of it is cut to a fixed
+    sample of its rows (seeded, sorted; the row numbers go to <name>_rows.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    if sum(v.nbytes for v in arrays.values()) > DUMP_BUDGET:
+        share = DUMP_BUDGET // (2 * len(arrays))      # the row lists fit in the other half
+        rng = np.random.default_rng(DUMP_SEED)
+        for k in sorted(arrays):
+            v = arrays[k]
+            if v.nbytes > share:
+                keep = max(1, share // max(1, v[0].nbytes))
+                rows = np.sort(rng.choice(v.shape[0], size=keep, replace=False))
+                arrays[k] = v[rows]
+                arrays[k + "_rows"] = rows.astype(np.float64)
+    assert sum(v.nbytes for v in arrays.values()) <= DUMP_BUDGET
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in arrays.items()}
+
+
 # ---------------------------------------------------------------- GPU run
 def main():
     a = parse()
@@ -745,6 +792,15 @@ def main():
     ws = e.workspace_bytes() + 8 * (b.S * (b.n + b.m + 3 * max(b.nn, 1) + 4))
     ipm_diag = e.ipm_info()
     rl = roofline(b, kinfo, launches, ws, tag, a.profile_dir, ipm=ipm_diag)
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        # what PHBase.iterk_loop left after its last timed step, read once every figure above
+        # is taken (the readbacks flush the deferred x̄ / W step)
+        nx = ph.xbar_by_node()
+        dumped = dump_outputs(a.dump_outputs, {
+            "W": ph.W_array(), "xbar": np.stack([nx[nd] for nd in e.node_names]),
+            "nonants": ph.nonants_array(), "obj": e.host("obj"), "conv": np.array([np.nan if ph.conv is None else ph.conv])})
+        log(f"[bench] outputs written to {a.dump_outputs}: {json.dumps(dumped)}")
     # value: K timed PH iterations / the synchronised wall time of the whole timed region
     # (barrier + synchronize on both sides, max over ranks) -- every GPU iteration counted,
     # including the speculative solve's overlap; the median of the host's per-iteration
@@ -827,6 +883,8 @@ def main():
             "setup_s": t_setup,
             "roofline": rl,
             "cpu_baseline": cpu,
+            "full": a.full,
+            "outputs_dumped": dumped,
         }
         print(json.dumps(out), flush=True)
     # release the handle while the HIP runtime (and a profiler's tool) is still up, not in

@@ -91,3 +91,35 @@ def test_json_line_carries_checks_key():
     """The JSON line is built with the checks dict (serialisable as is)."""
     c = _observe(1.0, warmup=5)
     json.dumps(c)
+
+
+def test_plain_run_skips_what_full_adds(monkeypatch):
+    """Without --full the parsed options carry no self-check and no CPU baseline; --full
+    keeps today's defaults; --check on alone is an error, not a silent no-op."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.check, a.no_cpu_baseline, a.dump_outputs) == (3, 2, False, "off", True, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert a.full and a.check == "auto" and not a.no_cpu_baseline
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--check", "on"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_dump_outputs_budget_and_fixed_sample(tmp_path):
+    """Small outputs are written whole in float64; outputs over the budget are cut to the
+    same seeded rows on every call, their row numbers beside them."""
+    small = {"W": np.arange(12, dtype=np.float32).reshape(4, 3), "conv": np.array([0.5])}
+    assert bench.dump_outputs(str(tmp_path / "s"), small) == {"W": [4, 3], "conv": [1]}
+    w = np.load(tmp_path / "s" / "W.npy")
+    assert w.dtype == np.float64 and np.array_equal(w, small["W"])
+    rows = bench.DUMP_BUDGET // (8 * 1000) + 1                # one array just over the budget
+    big = {"x": np.arange(rows * 1000, dtype=np.float64).reshape(rows, 1000), "obj": np.ones(rows)}
+    for d in ("a", "b"):
+        shapes = bench.dump_outputs(str(tmp_path / d), big)
+    x, r = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "a" / "x_rows.npy")
+    assert shapes["obj"] == [rows] and x.shape[0] == len(r) < rows and np.all(np.diff(r) > 0)
+    assert np.array_equal(x, big["x"][r.astype(int)])
+    assert np.array_equal(r, np.load(tmp_path / "b" / "x_rows.npy"))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_BUDGET

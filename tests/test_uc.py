@@ -9,7 +9,18 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = json.load(open(os.path.join(HERE, "golden", "uc.json")))
-REF = "/root/reference/paperruns/larger_uc"
+
+
+@pytest.fixture(scope="module")
+def ref_dir(tmp_path_factory):
+    """RootNode.dat and Node<k>.dat (k = 1, 17, 500, 1000) of the reference's
+    paperruns/larger_uc data, unpacked from tests/golden/uc_dat.zip into one directory (what
+    uc.load_data's ``path`` takes): the packed copies must say what the files say."""
+    import zipfile
+    d = tmp_path_factory.mktemp("uc_dat")
+    with zipfile.ZipFile(os.path.join(HERE, "golden", "uc_dat.zip")) as z:
+        z.extractall(d)
+    return str(d)
 
 
 def test_dat_reader_forms():
@@ -44,18 +55,16 @@ def test_root_node_data():
     assert d.min_prod_cost[g] == pytest.approx(7709.70375 * 0.00227)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference data not present")
-def test_packed_root_data_matches_root_node_file():
+def test_packed_root_data_matches_root_node_file(ref_dir):
     from mpisppy_amd.examples import uc
-    assert uc._root_data(None) == uc._root_data(REF)
+    assert uc._root_data(None) == uc._root_data(ref_dir)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference data not present")
-def test_packed_wind_matches_node_files():
+def test_packed_wind_matches_node_files(ref_dir):
     from mpisppy_amd.examples import uc
     for k in (1, 17, 500, 1000):
         packed = uc.wind_bounds(k)
-        files = uc.wind_bounds(k, path=os.path.join(REF, "1000scenarios_wind"))
+        files = uc.wind_bounds(k, path=ref_dir)
         for i in (0, 1):
             assert packed[i] == {key: float(v) for key, v in files[i].items()}
 

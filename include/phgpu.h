@@ -164,8 +164,9 @@ int phgpu_set_scenarios(phgpu_handle h, const double* A_val, const double* c,
 int phgpu_set_nonant_probs(phgpu_handle h, const double* pvar);
 
 /* Interior-point tuning of this handle (path 6): defs = "IPM_NAME=number;..." -- the
- * compile-time constants of the generated interior-point modules (jit_ipm*.hip.in:
- * IPM_SIG_MIN, IPM_WARM_T, ...) for the modules this handle builds; a model's measured
+ * compile-time constants of the generated interior-point modules (one table of defaults
+ * for every kernel, jit_ipm_common.hip.in: IPM_SIG_MIN, IPM_WARM_T, ...; a kernel's own in
+ * its jit_ipm*.hip.in) for the modules this handle builds; a model's measured
  * values (examples/aircond.py IPM_TUNING).  Only IPM_ names and numeric values; NULL or ""
  * clears.  Call before the first solve (-1 once the module is built).  The PHGPU_IPM_DEFS
  * environment variable (experiments) overrides it name by name. */

@@ -3036,29 +3036,9 @@ extern "C" int phgpu_ph_loop(phgpu_handle h, const phgpu_options* opt, int max_i
     P.wmin = 1.0 / P.wmax;
     const int par = h->ipm_parity;
     h->ipm_parity ^= 1;
-    int32_t* fail_n = h->ipm_cnt + 3 * par;
-    int32_t* qhead = h->ipm_cnt + 3 * par + 1;
-    ipm_params_host a;
-    a.A = h->A; a.c = h->c; a.q = h->q; a.lb = h->lb; a.ub = h->ub; a.rl = h->rl; a.ru = h->ru; a.objc = h->objc;
-    a.lbh = h->lbh; a.ubh = h->ubh; a.Dc = h->Dc; a.Dr = h->Dr;
-    a.W = h->W; a.rho = h->rho; a.xbar = h->xbar;
-    a.omega_in = h->omega;
-    a.omega_out = h->omega_w; a.x_w = h->xw; a.y_w = h->yw;
-    a.xout = x; a.yout = y; a.obj = obj; a.bound = bound;
-    a.status = status; a.iters = iters;
-    a.fail_list = h->ipm_list; a.fail_n = fail_n;
-    a.zero3 = h->ipm_cnt + 3 * (1 - par);
-    a.stats = h->ipm_stats + PHGPU_STATS_WORDS * par; a.stats_zero = h->ipm_stats + PHGPU_STATS_WORDS * (1 - par);
+    ipm_params a{};
+    ipm_fill_args(h, P, par, x, y, obj, bound, status, iters, a);
     a.prof = nullptr;
-    a.S = h->S;
-    a.W_on = h->W_on; a.prox_on = h->prox_on;
-    a.eps_rel = P.eps_rel; a.eps_abs = P.eps_abs;
-    const char* et = getenv("PHGPU_IPM_EPS");
-    a.eps_tight = (et && atof(et) > 0.0) ? atof(et) : IPM_EPS_TIGHT;
-    a.x_in = P.warm ? h->x : nullptr;
-    a.y_in = P.warm ? h->y : nullptr;
-    const char* env = getenv("PHGPU_IPM_MAXIT");
-    a.max_ipm = (env && atoi(env) >= 0) ? atoi(env) : IPM_MAXIT;
     a.xp = nullptr;  // (no epilogue partials: the loop ends on its own PH state)
     a.xp_node = h->xp_node[wq];
     a.xp_dirty = h->xp_dirty[wq];
@@ -3080,11 +3060,10 @@ extern "C" int phgpu_ph_loop(phgpu_handle h, const phgpu_options* opt, int max_i
     a.convthresh = convthresh;
     a.loop_K = max_iters;
     h->xp_C[wq] = 0;
-    h->last_stats = a.stats;
     void* args[] = {&a};
     HIPCHK(hipModuleLaunchCooperativeKernel(im->fn_ipm, (unsigned)nblk, 1, 1, 256, 1, 1, 0, st, args));
     {
-        const int rc = ipm_fallback_launch(h, im, P, x, y, obj, bound, status, iters, qhead, fail_n, a.stats, st);
+        const int rc = ipm_fallback_launch(h, im, P, x, y, obj, bound, status, iters, a.fail_n + 1, a.fail_n, a.stats, st);
         if (rc) return rc;
     }
     HIPCHK(hipGetLastError());

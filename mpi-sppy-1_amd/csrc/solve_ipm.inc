@@ -17,6 +17,12 @@
 //     max_ipm iterations, or an iterate that stopped being finite -- infeasible and
 //     unbounded scenarios end there and get their certificates from the PDHG).
 //
+// What the kernel templates (jit_ipm.hip.in, jit_ipm_ml.hip.in, jit_ipm_wave.hip.in,
+// jit_ipm_blk.hip.in) have in common is written once and emitted into every module ahead of
+// them: the argument blocks (ipm_args.h, which this file includes too, so the host fills the
+// very structs the kernels read -- ipm_fill_args) and the iteration's tunables, statistics
+// and reciprocals (jit_ipm_common.hip.in).
+//
 // The module is compiled at the first path-6 solve (one synchronisation for the data
 // flags) and cached under its source text; phgpu_set_scenarios invalidates the flags.
 // Nonant bounds are always read per lane (phgpu_fix_nonants changes them without a
@@ -26,6 +32,33 @@
 
 #include <array>
 
+// The kernels' argument blocks -- ph_step, the layers ipmw_params < ipm_step_params <
+// ipm_params, and the lane-group kernel's ipml_params -- are one text, ipm_args.h (the
+// names are the kernels' own of old, which the tests' host emulations spell; their host
+// twins are gone): included here for the host, and embedded
+// (kIpmArgs) for ipm_source to put into every module, so the two sides cannot disagree.
+// The asserts pin the layout the kernels were measured with: changing it is deliberate.
+#include "ipm_args.h"
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"  // (the derived layers are not standard-layout)
+static_assert(sizeof(ph_step) == 136 && offsetof(ph_step, node_buf) == 48 && offsetof(ph_step, cnt) == 128,
+              "ph_step changed its layout");
+static_assert(sizeof(ipmw_params) == 304 && offsetof(ipmw_params, S) == 224 &&
+                  offsetof(ipmw_params, x_in) == 272 && offsetof(ipmw_params, stats_zero) == 296,
+              "ipmw_params changed its layout");
+static_assert(sizeof(ipm_step_params) == 488 && offsetof(ipm_step_params, xp) == 304 &&
+                  offsetof(ipm_step_params, ph) == 344 && offsetof(ipm_step_params, prof) == 480,
+              "ipm_step_params changed its layout");
+static_assert(sizeof(ipml_params) == 496 && offsetof(ipml_params, unused) == 224 && offsetof(ipml_params, S) == 232 &&
+                  offsetof(ipml_params, xp) == 312 && offsetof(ipml_params, prof) == 488,
+              "ipml_params changed its layout");
+static_assert(sizeof(ipm_params) == 608 && offsetof(ipm_params, xprev) == 488 &&
+                  offsetof(ipm_params, gsync) == 576 && offsetof(ipm_params, loop_K) == 600,
+              "ipm_params changed its layout");
+#pragma clang diagnostic pop
+
+#include "ipm_args.inc"
+#include "ipm_common.inc"
 #include "ipm_kernel.inc"
 #include "ipm_ml_kernel.inc"
 #include "ph_step_kernel.inc"
@@ -83,87 +116,6 @@ static int ipm_spill_max() {
 #define IPM_ML_LANES 8
 #define IPM_FALLBACK_BLOCKS 16  // workgroups of the fallback launch (4,096 lanes)
 #define IPM_EPS_TIGHT 1e-13  // the IPM's own target (PHGPU_IPM_EPS), see jit_ipm.hip.in
-
-// host mirror of ph_step (jit_ph_step.hip.in): same member order and types
-struct ph_step_host {
-    int on = 0, update_W = 0;
-    const double* xprev = nullptr;
-    const double* xp = nullptr;
-    const int* xp_dirty = nullptr;
-    long long xp_n = 0;
-    int C = 0;
-    double* node_buf = nullptr;
-    const int* nb_idx = nullptr;
-    long long nb_half = 0;
-    double *W = nullptr, *xbar = nullptr;
-    const double* rho = nullptr;
-    double* conv = nullptr;
-    long long* stats_dst = nullptr;
-    double scale = 0.0;
-    double* cpart = nullptr;
-    int* cnt = nullptr;
-};
-
-// host mirror of ipml_params (jit_ipm_ml.hip.in)
-struct ipml_params_host {
-    const double *A, *c, *q, *lb, *ub, *rl, *ru, *objc;
-    const double *lbh, *ubh, *Dc, *Dr;
-    const double *W, *rho, *xbar;
-    const double* omega_in;
-    double *omega_out, *x_w, *y_w;
-    double *xout, *yout, *obj, *bound;
-    int *status, *iters;
-    int *fail_list, *fail_n, *zero3, *qhead;
-    long long S;
-    int W_on, prox_on;
-    double eps_rel, eps_abs, eps_tight;
-    int max_ipm;
-    const double *x_in, *y_in;
-    unsigned long long *stats, *stats_zero;
-    double* xp;
-    int *xp_node, *xp_dirty;
-    const double* pcoef;
-    const int* node_of;
-    ph_step_host ph;
-    unsigned long long* prof;
-};
-
-// host mirror of ipm_params (jit_ipm.hip.in): same member order and types
-struct ipm_params_host {
-    const double *A, *c, *q, *lb, *ub, *rl, *ru, *objc;
-    const double *lbh, *ubh, *Dc, *Dr;
-    const double *W, *rho, *xbar;
-    const double* omega_in;
-    double *omega_out, *x_w, *y_w;
-    double *xout, *yout, *obj, *bound;
-    int *status, *iters;
-    int *fail_list, *fail_n, *zero3;
-    long long S;
-    int W_on, prox_on;
-    double eps_rel, eps_abs, eps_tight;
-    int max_ipm;
-    const double *x_in, *y_in;
-    unsigned long long *stats, *stats_zero;
-    double* xp;
-    int *xp_node, *xp_dirty;
-    const double* pcoef;
-    const int* node_of;
-    ph_step_host ph;
-    unsigned long long* prof;
-    // IPM_LOOP (phgpu_ph_loop)
-    const double* xprev = nullptr;
-    double *W_w = nullptr, *xbar_w = nullptr;
-    double* node_buf = nullptr;
-    const int* nb_idx = nullptr;
-    long long nb_half = 0;
-    double* conv_hist = nullptr;
-    int* loop_out = nullptr;
-    unsigned long long* loop_its = nullptr;
-    double *gpart = nullptr, *gpub = nullptr;
-    unsigned* gsync = nullptr;
-    double conv_scale = 0.0, convthresh = 0.0;
-    int loop_K = 0;
-};
 
 struct ipm_module {
     std::string key;  // the generated source the module was built from
@@ -567,7 +519,7 @@ static std::string ipm_table(const char* type, const char* name, const std::vect
 
 // NN and the nonants' columns / depths for the x̄ partials of the IPM epilogues
 // (nonant k is the column j with slot[j] == k; ndep[k] its tree depth, null = 0)
-static std::string ipm_nonant_defs(int n, const int32_t* slot, const int32_t* ndep, bool tables) {
+static std::string ipm_nonant_defs(int n, const int32_t* slot, const int32_t* ndep) {
     int nn = 0;
     for (int j = 0; j < n; ++j) nn = std::max(nn, slot[j] + 1);
     std::vector<std::string> col(std::max(nn, 1), "0"), dep(std::max(nn, 1), "0");
@@ -581,12 +533,10 @@ static std::string ipm_nonant_defs(int n, const int32_t* slot, const int32_t* nd
     std::vector<int> colv(std::max(nn, 1), 0);
     for (int j = 0; j < n; ++j)
         if (slot[j] >= 0) colv[slot[j]] = j;
-    (void)tables;
     std::string s = "#define NN " + std::to_string(nn) + "\n";
     s += ipm_table<int>("int", "NDEP", depv, [](int v) { return std::to_string(v); });
     s += ipm_table<int>("int", "NCOLT", colv, [](int v) { return std::to_string(v); });
-    return s + "#define INCOL(k) " + ipm_chain("k", col) + "\n#define INDEP(k) " + ipm_chain("k", dep) + "\n" +
-           kPhStep;
+    return s + "#define INCOL(k) " + ipm_chain("k", col) + "\n#define INDEP(k) " + ipm_chain("k", dep) + "\n";
 }
 
 // the preamble of the IPM kernel (everything jit_ipm.hip.in expects); info[0] = active
@@ -988,8 +938,13 @@ static int ipm_wg_bound(int n, int m, int nnz, const int32_t* rp, const int32_t*
 
 // The whole source of a handle's path-6 module: the path-5 preamble and kernel (the
 // fallback) followed by the IPM preamble and kernel; for the workgroup kernel (L >= 64 =
-// its threads per scenario) the IPM alone (its fallback is k_solve over the list).  Pure
-// host code (no GPU).
+// its threads per scenario) the IPM alone (its fallback is k_solve over the list).  Every
+// IPM preamble starts with its #define IPM_GAM line and carries the tuning definitions
+// (ipm_env_defs); after it come, once each, the argument blocks (ipm_args.h), the folded PH
+// step (one lane / lane groups), the shared defaults and helpers (jit_ipm_common.hip.in,
+// all #ifndef: the tuning comes first) and the kernel template, whose first line is its
+// "// <file> --" banner (the host emulations and tools cut the source at those two marks).
+// Pure host code (no GPU).
 static std::string ipm_source_body(int n, int m, int nnz, const int32_t* rp, const int32_t* ci, const int32_t* slot,
                                    const int32_t* kinds, const int32_t* flags, const double* v0, int* info,
                                    int L, const int32_t* ndep);
@@ -1013,17 +968,22 @@ static std::string ipm_source_body(int n, int m, int nnz, const int32_t* rp, con
         const char* be = getenv("PHGPU_IPM_BLK");
         if (!(be && atoi(be) == 0)) {
             const std::string pre = ipm_blk_preamble(n, m, nnz, rp, ci, slot, flags, v0, info, L, &ok);
-            if (ok) return pre + kIpmWgCommon + kIpmBlkKernel;
+            if (ok) return pre + kIpmArgs + kIpmCommon + kIpmWgCommon + kIpmBlkKernel;
         }
         const std::string pre = ipm_wave_preamble(n, m, nnz, rp, ci, slot, flags, v0, info, &ok, L / 64);
-        return ok ? pre + kIpmWgCommon + kIpmWaveKernel : std::string();
+        return ok ? pre + kIpmArgs + kIpmCommon + kIpmWgCommon + kIpmWaveKernel : std::string();
     }
     std::vector<int32_t> rpv(rp, rp + m + 1), civ(ci, ci + std::max(nnz, 1)), sv(slot, slot + n), kv(kinds, kinds + n + m);
     if (!nnz) civ.assign(1, 0);
-    std::string src = jit_preamble(n, m, nnz, rpv, civ, sv, kv, 1) + kJitKernel;
+    std::string src = jit_source(jit_preamble(n, m, nnz, rpv, civ, sv, kv, 1));
     src += "\n#undef NC\n#undef NR\n#undef NZ\n";
-    if (L <= 1) src += ipm_preamble(n, m, nnz, rp, ci, slot, flags, v0, 1, info) + ipm_nonant_defs(n, slot, ndep, false) + kIpmKernel;
-    else src += ipm_ml_preamble(n, m, nnz, rp, ci, slot, flags, v0, L, info) + ipm_nonant_defs(n, slot, ndep, true) + kIpmMlKernel;
+    src += L <= 1 ? ipm_preamble(n, m, nnz, rp, ci, slot, flags, v0, 1, info)
+                  : ipm_ml_preamble(n, m, nnz, rp, ci, slot, flags, v0, L, info);
+    src += ipm_nonant_defs(n, slot, ndep);
+    src += kIpmArgs;
+    src += kPhStep;
+    src += kIpmCommon;
+    src += L <= 1 ? kIpmKernel : kIpmMlKernel;
     return src;
 }
 
@@ -1092,6 +1052,38 @@ static int ipm_lanes(const phgpu_state* h) {
 // phgpu_set_ipm_tuning's definitions, by handle (host side: the state is a kernel argument)
 static std::map<const phgpu_state*, std::string> g_ipm_tuning_of;
 
+// Compile a path-6 source and load it: the IPM kernel `fname` (L lanes / threads per
+// scenario) with its occupancy and resources and, when want_pdhg, the module's path-5 kernel
+// (the fallback).  *out is the new module (key = src); mr / nf / flops are the caller's.
+static int ipm_module_load(const std::string& src, int L, const char* fname, bool want_pdhg, const char* what,
+                           ipm_module** out) {
+    std::vector<char> code;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = jit_compile(src, code, L == 1);
+    if (rc) return rc;
+    ipm_module* im = new ipm_module();
+    im->compile_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    im->key = src;
+    im->L = L;
+    hipError_t e = hipModuleLoadData(&im->mod, code.data());
+    if (e == hipSuccess) e = hipModuleGetFunction(&im->fn_ipm, im->mod, fname);
+    if (e == hipSuccess)
+        e = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&im->per_cu_ipm, im->fn_ipm, L < 64 ? 256 : L, 0);
+    if (want_pdhg) {
+        if (e == hipSuccess) e = hipModuleGetFunction(&im->fn_pdhg, im->mod, "k_solve_jit");
+        if (e == hipSuccess) e = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&im->per_cu_pdhg, im->fn_pdhg, 256, 0);
+    }
+    if (e == hipSuccess) e = hipFuncGetAttribute(&im->private_bytes, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, im->fn_ipm);
+    if (e == hipSuccess) e = hipFuncGetAttribute(&im->vgprs, HIP_FUNC_ATTRIBUTE_NUM_REGS, im->fn_ipm);
+    if (e != hipSuccess) {
+        if (im->mod) (void)hipModuleUnload(im->mod);
+        delete im;
+        return set_err(-2, "loading the %s module failed: %s", what, hipGetErrorString(e));
+    }
+    *out = im;
+    return 0;
+}
+
 static int ipm_prepare(phgpu_state* h, hipStream_t st) {
     if (h->ipm && h->ipm_flags_valid && h->ipm->L == ipm_lanes(h)) return 0;
     struct tuning_scope {
@@ -1138,37 +1130,17 @@ static int ipm_prepare(phgpu_state* h, hipStream_t st) {
         h->ipm_flags_valid = 1;
         return 0;
     }
-    std::vector<char> code;
-    const auto t0 = std::chrono::steady_clock::now();
-    const int rc = jit_compile(src, code, L == 1);
+    const bool blk = L >= 64 && src.find("k_solve_ipm_blk") != std::string::npos;
+    const char* fname = L == 1 ? "k_solve_ipm" : (L < 64 ? "k_solve_ipm_ml" : (blk ? "k_solve_ipm_blk" : "k_solve_ipm_wave"));
+    ipm_module* im = nullptr;
+    // (the workgroup kernels' fallback is k_solve of the library, not the module's path 5)
+    const int rc = ipm_module_load(src, L, fname, L < 64, "path-6", &im);
     if (rc) return rc;
-    ipm_module* im = new ipm_module();
-    im->compile_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    im->key = src;
-    im->L = L;
+    im->blk = blk;
     im->mr = inf[0];
     im->nf = inf[1];
     im->fac_flops = inf[2];
     im->sol_flops = inf[3];
-    hipError_t e = hipModuleLoadData(&im->mod, code.data());
-    const char* fname = L == 1 ? "k_solve_ipm"
-                      : (L < 64 ? "k_solve_ipm_ml"
-                                : (src.find("k_solve_ipm_blk") != std::string::npos ? "k_solve_ipm_blk" : "k_solve_ipm_wave"));
-    im->blk = L >= 64 && src.find("k_solve_ipm_blk") != std::string::npos;
-    if (e == hipSuccess) e = hipModuleGetFunction(&im->fn_ipm, im->mod, fname);
-    if (e == hipSuccess)
-        e = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&im->per_cu_ipm, im->fn_ipm, L < 64 ? 256 : L, 0);
-    if (L < 64) {  // the workgroup kernel's fallback is k_solve (library), not the module's path 5
-        if (e == hipSuccess) e = hipModuleGetFunction(&im->fn_pdhg, im->mod, "k_solve_jit");
-        if (e == hipSuccess) e = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&im->per_cu_pdhg, im->fn_pdhg, 256, 0);
-    }
-    if (e == hipSuccess) e = hipFuncGetAttribute(&im->private_bytes, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, im->fn_ipm);
-    if (e == hipSuccess) e = hipFuncGetAttribute(&im->vgprs, HIP_FUNC_ATTRIBUTE_NUM_REGS, im->fn_ipm);
-    if (e != hipSuccess) {
-        if (im->mod) (void)hipModuleUnload(im->mod);
-        delete im;
-        return set_err(-2, "loading the path-6 module failed: %s", hipGetErrorString(e));
-    }
     if (h->ipm) {
         (void)hipModuleUnload(h->ipm->mod);
         delete h->ipm;
@@ -1209,7 +1181,7 @@ static int ipm_prepare(phgpu_state* h, hipStream_t st) {
 static int ipm_fallback_launch(phgpu_state* h, ipm_module* im, const solve_params& P, double* x, double* y,
                                double* obj, double* bound, int32_t* status, int32_t* iters, int32_t* qhead,
                                int32_t* fail_n, unsigned long long* stats, hipStream_t st) {
-    jit_params_host b;
+    jit_params b{};
     b.A = h->Ah_csr; b.c = h->c; b.q = h->q; b.Dc = h->Dc; b.lbh = h->lbh; b.ubh = h->ubh; b.Dr = h->Dr;
     b.rlh = h->rlh; b.ruh = h->ruh; b.rl = h->rl; b.ru = h->ru; b.objc = h->objc; b.normA = h->normA;
     b.W = h->W; b.rho = h->rho; b.xbar = h->xbar;
@@ -1237,16 +1209,13 @@ static int ipm_fallback_launch(phgpu_state* h, ipm_module* im, const solve_param
     return 0;
 }
 
-static int ipm_launch(phgpu_state* h, const solve_params& P, double* x, double* y, double* obj, double* bound,
-                      int32_t* status, int32_t* iters, hipStream_t st) {
-    ipm_module* im = h->ipm;
-    const int par = h->ipm_parity;
-    h->ipm_parity ^= 1;
-    // this solve's counters {fallback count, fallback queue head, IPM queue head}: zeroed by
-    // the previous path-6 launch (the other parity) or at create
-    int32_t* fail_n = h->ipm_cnt + 3 * par;
-    int32_t* qhead = h->ipm_cnt + 3 * par + 1;
-    ipm_params_host a;
+// The core of a path-6 launch's argument block (and prof) for the solve of parity par, the
+// one place that reads PHGPU_IPM_EPS / PHGPU_IPM_MAXIT and does the parity arithmetic: this
+// solve's counters {fallback count, fallback queue head, spare} and statistics are those of
+// its parity, zeroed by the previous path-6 launch (the other parity) or at create; the
+// kernel zeroes the other parity's for the next.  Sets h->last_stats.
+static void ipm_fill_args(phgpu_state* h, const solve_params& P, int par, double* x, double* y, double* obj,
+                          double* bound, int32_t* status, int32_t* iters, ipm_step_params& a) {
     a.A = h->A; a.c = h->c; a.q = h->q; a.lb = h->lb; a.ub = h->ub; a.rl = h->rl; a.ru = h->ru; a.objc = h->objc;
     a.lbh = h->lbh; a.ubh = h->ubh; a.Dc = h->Dc; a.Dr = h->Dr;
     a.W = h->W; a.rho = h->rho; a.xbar = h->xbar;
@@ -1254,7 +1223,7 @@ static int ipm_launch(phgpu_state* h, const solve_params& P, double* x, double* 
     a.omega_out = h->omega_w; a.x_w = h->xw; a.y_w = h->yw;
     a.xout = x; a.yout = y; a.obj = obj; a.bound = bound;
     a.status = status; a.iters = iters;
-    a.fail_list = h->ipm_list; a.fail_n = fail_n;
+    a.fail_list = h->ipm_list; a.fail_n = h->ipm_cnt + 3 * par;
     a.zero3 = h->ipm_cnt + 3 * (1 - par);
     a.stats = h->ipm_stats + PHGPU_STATS_WORDS * par; a.stats_zero = h->ipm_stats + PHGPU_STATS_WORDS * (1 - par);
     a.prof = h->ipm_prof;  // IPM_PROF modules only (phgpu_ipm_prof), null unless PHGPU_IPM_PROF
@@ -1268,11 +1237,24 @@ static int ipm_launch(phgpu_state* h, const solve_params& P, double* x, double* 
     a.y_in = P.warm ? h->y : nullptr;
     const char* env = getenv("PHGPU_IPM_MAXIT");
     a.max_ipm = (env && atoi(env) >= 0) ? atoi(env) : IPM_MAXIT;
+}
+
+static int ipm_launch(phgpu_state* h, const solve_params& P, double* x, double* y, double* obj, double* bound,
+                      int32_t* status, int32_t* iters, hipStream_t st) {
+    ipm_module* im = h->ipm;
+    const int par = h->ipm_parity;
+    h->ipm_parity ^= 1;
+    // every path-6 launch is filled as this one block: the one-lane kernel reads all of it
+    // (and ignores the loop's tail), the workgroup kernels take its core layer, the lane-group
+    // kernel a copy of its step layer's parts
+    ipm_params a{};
+    ipm_fill_args(h, P, par, x, y, obj, bound, status, iters, a);
+    int32_t* qhead = a.fail_n + 1;  // the fallback's queue head
     if (im->L >= 64) {
-        // the workgroup kernel (one scenario per workgroup of L threads); its param struct
-        // is the prefix of ipm_params up to stats_zero (jit_ipm_wave.hip.in ipmw_params)
+        // the workgroup kernels (one scenario per workgroup of L threads) take the core layer
         h->xp_C[h->wq] = 0;
-        void* args[] = {&a};
+        ipmw_params& core = a;
+        void* args[] = {&core};
         HIPCHK(hipModuleLaunchKernel(im->fn_ipm, (unsigned)h->S, 1, 1, (unsigned)im->L, 1, 1, 0, st, args, nullptr));
         // the fallback: the global-memory PDHG (path 1) over the list, warm-started from the
         // IPM's hand-over (x_w / y_w / omega_w), adding its scenarios' statistics
@@ -1284,7 +1266,7 @@ static int ipm_launch(phgpu_state* h, const solve_params& P, double* x, double* 
         Q.warm = 1;
         hipLaunchKernelGGL(k_solve, dim3((unsigned)((h->S + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, v, Q, x, y, obj,
                            bound, status, iters,
-                           (const int32_t*)h->ipm_list, (const int32_t*)fail_n, a.stats);
+                           (const int32_t*)h->ipm_list, (const int32_t*)a.fail_n, a.stats);
         HIPCHK(hipGetLastError());
         return 0;
     }
@@ -1329,31 +1311,15 @@ static int ipm_launch(phgpu_state* h, const solve_params& P, double* x, double* 
     h->xp_C[wq] = xp_on ? C : 0;
     h->xp_x[wq] = x;
     h->xp_n[wq] = (h->S + C - 1) / C;
-    if (im->L == 1) {
-        void* args[] = {&a};
-        const unsigned nblk = (unsigned)((h->S + 255) / 256);
-        HIPCHK(hipModuleLaunchKernel(im->fn_ipm, nblk, 1, 1, 256, 1, 1, 0, st, args, nullptr));
-    } else {
-        // lane groups
-        ipml_params_host ml;
-        ml.A = a.A; ml.c = a.c; ml.q = a.q; ml.lb = a.lb; ml.ub = a.ub; ml.rl = a.rl; ml.ru = a.ru; ml.objc = a.objc;
-        ml.lbh = a.lbh; ml.ubh = a.ubh; ml.Dc = a.Dc; ml.Dr = a.Dr; ml.W = a.W; ml.rho = a.rho; ml.xbar = a.xbar;
-        ml.omega_in = a.omega_in; ml.omega_out = a.omega_out; ml.x_w = a.x_w; ml.y_w = a.y_w;
-        ml.xout = x; ml.yout = y; ml.obj = obj; ml.bound = bound; ml.status = status; ml.iters = iters;
-        ml.fail_list = a.fail_list; ml.fail_n = fail_n; ml.zero3 = a.zero3; ml.qhead = h->ipm_cnt + 3 * par + 2;
-        ml.S = a.S; ml.W_on = a.W_on; ml.prox_on = a.prox_on;
-        ml.eps_rel = a.eps_rel; ml.eps_abs = a.eps_abs; ml.eps_tight = a.eps_tight; ml.max_ipm = a.max_ipm;
-        ml.x_in = a.x_in; ml.y_in = a.y_in; ml.stats = a.stats; ml.stats_zero = a.stats_zero;
-        ml.xp = a.xp; ml.xp_node = a.xp_node; ml.xp_dirty = a.xp_dirty; ml.pcoef = a.pcoef; ml.node_of = a.node_of;
-        ml.ph = a.ph;
-        ml.prof = a.prof;
-        // one scenario per group: S * L lanes (k_solve_ipm_ml has no queue since its
-        // load / iterate / store phases split; ml.qhead is unused)
-        const unsigned nblk = (unsigned)((h->S * im->L + 255) / 256);
-        void* args[] = {&ml};
-        HIPCHK(hipModuleLaunchKernel(im->fn_ipm, nblk, 1, 1, 256, 1, 1, 0, st, args, nullptr));
-    }
-    return ipm_fallback_launch(h, im, P, x, y, obj, bound, status, iters, qhead, fail_n, a.stats, st);
+    // one lane: a scenario per lane; lane groups: one scenario per group, S * L lanes
+    ipml_params ml{};
+    static_cast<ipm_params_ptrs&>(ml) = a;
+    static_cast<ipm_params_ctl&>(ml) = a;
+    static_cast<ipm_params_xp&>(ml) = a;
+    void* args[] = {im->L == 1 ? (void*)&a : (void*)&ml};
+    const unsigned nblk = (unsigned)((h->S * im->L + 255) / 256);
+    HIPCHK(hipModuleLaunchKernel(im->fn_ipm, nblk, 1, 1, 256, 1, 1, 0, st, args, nullptr));
+    return ipm_fallback_launch(h, im, P, x, y, obj, bound, status, iters, qhead, a.fail_n, a.stats, st);
 }
 
 // ---------------------------------------------------------------- the PH loop (IPM_LOOP)
@@ -1362,30 +1328,13 @@ static int ipm_launch(phgpu_state* h, const solve_params& P, double* x, double* 
 static int ipm_loop_prepare(phgpu_state* h) {
     const std::string src = "#define IPM_LOOP 1\n" + h->ipm->key;
     if (h->ipm_loop && h->ipm_loop->key == src) return 0;
-    std::vector<char> code;
-    const auto t0 = std::chrono::steady_clock::now();
-    const int rc = jit_compile(src, code, true);
+    ipm_module* im = nullptr;
+    const int rc = ipm_module_load(src, 1, "k_ph_loop_ipm", true, "PH-loop", &im);
     if (rc) return rc;
-    ipm_module* im = new ipm_module();
-    im->compile_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    im->key = src;
-    im->L = 1;
     im->mr = h->ipm->mr;
     im->nf = h->ipm->nf;
     im->fac_flops = h->ipm->fac_flops;
     im->sol_flops = h->ipm->sol_flops;
-    hipError_t e = hipModuleLoadData(&im->mod, code.data());
-    if (e == hipSuccess) e = hipModuleGetFunction(&im->fn_ipm, im->mod, "k_ph_loop_ipm");
-    if (e == hipSuccess) e = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&im->per_cu_ipm, im->fn_ipm, 256, 0);
-    if (e == hipSuccess) e = hipModuleGetFunction(&im->fn_pdhg, im->mod, "k_solve_jit");
-    if (e == hipSuccess) e = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&im->per_cu_pdhg, im->fn_pdhg, 256, 0);
-    if (e == hipSuccess) e = hipFuncGetAttribute(&im->private_bytes, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, im->fn_ipm);
-    if (e == hipSuccess) e = hipFuncGetAttribute(&im->vgprs, HIP_FUNC_ATTRIBUTE_NUM_REGS, im->fn_ipm);
-    if (e != hipSuccess) {
-        if (im->mod) (void)hipModuleUnload(im->mod);
-        delete im;
-        return set_err(-2, "loading the PH-loop module failed: %s", hipGetErrorString(e));
-    }
     if (h->ipm_loop) {
         (void)hipModuleUnload(h->ipm_loop->mod);
         delete h->ipm_loop;

@@ -18,6 +18,14 @@
 #include <hip/hiprtc.h>
 #include <string>
 
+// jit_params, the kernel's argument block: this very text (jit_args.h, embedded as kJitArgs)
+// is what jit_source puts ahead of the kernel, so host and device cannot disagree on it.
+// The asserts make a change of its layout a deliberate one.
+#include "jit_args.h"
+static_assert(sizeof(jit_params) == 384 && offsetof(jit_params, S) == 256 && offsetof(jit_params, eps_rel) == 280 &&
+                  offsetof(jit_params, max_iter) == 360,
+              "jit_params changed its layout");
+#include "jit_args.inc"
 #include "jit_kernel.inc"
 
 // limits of the specialisation: the per-lane state must fit the register file
@@ -27,22 +35,6 @@
 #define JIT_MAX_N 48
 #define JIT_MAX_M 48
 #define JIT_MAX_NNZ 128
-
-// host mirror of jit_params (jit_kernel.hip.in): same member order and types
-struct jit_params_host {
-    const double *A, *c, *q, *Dc, *lbh, *ubh, *Dr, *rlh, *ruh, *rl, *ru, *objc, *normA;
-    const double *W, *rho, *xbar;
-    const double *omega_in, *x_in, *y_in;
-    double *omega_out, *x_w, *y_w;
-    double *xout, *yout, *obj, *bound;
-    int *status, *iters, *qhead;
-    const int *list, *list_n;
-    unsigned long long* stats;
-    long long S, first_dyn;
-    int W_on, prox_on;
-    double eps_rel, eps_abs, bsuff, bnec, bart, eta_frac, omega0, wmin, wmax, eps_inf;
-    int max_iter, check_every, restart_every, warm, keep_omega, infeas_start;
-};
 
 struct jit_module {
     std::string key;       // pattern + kinds the module was built for
@@ -136,6 +128,9 @@ static std::string jit_preamble(int n, int m, int nnz, const std::vector<int32_t
     return s;
 }
 
+// a path-5 module's source: the generated preamble, the argument block, the kernel
+static std::string jit_source(const std::string& pre) { return pre + kJitArgs + kJitKernel; }
+
 static int jit_compile(const std::string& src, std::vector<char>& code, bool max_ilp = false) {
     hiprtcProgram prog;
     if (hiprtcCreateProgram(&prog, src.c_str(), "phgpu_jit.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS)
@@ -203,7 +198,7 @@ static int jit_prepare(phgpu_state* h, hipStream_t st) {
     }
     std::vector<char> code;
     const auto t0 = std::chrono::steady_clock::now();
-    const int rc = jit_compile(pre + kJitKernel, code);
+    const int rc = jit_compile(jit_source(pre), code);
     if (rc) return rc;
     jit_module* jm = new jit_module();
     jm->compile_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -231,7 +226,7 @@ static int jit_launch(phgpu_state* h, const solve_params& P, double* x, double* 
     jit_module* jm = h->jit;
     const int64_t per = (int64_t)(jm->per_cu < 1 ? 1 : jm->per_cu) * h->num_cus * 256;
     int64_t nblk = (std::min<int64_t>(per, h->S) + 255) / 256;
-    jit_params_host a;
+    jit_params a{};
     a.A = h->Ah_csr; a.c = h->c; a.q = h->q; a.Dc = h->Dc; a.lbh = h->lbh; a.ubh = h->ubh; a.Dr = h->Dr;
     a.rlh = h->rlh; a.ruh = h->ruh; a.rl = h->rl; a.ru = h->ru; a.objc = h->objc; a.normA = h->normA;
     a.W = h->W; a.rho = h->rho; a.xbar = h->xbar;

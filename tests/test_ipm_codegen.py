@@ -54,6 +54,64 @@ def test_generated_module_compiles_for_gfx950_without_scratch(tmp_path):
     assert scratch == 0, ipm[0][:1500]
 
 
+def _wg_batch():
+    from test_gpu_ipm_wave import arrow_batch
+    return arrow_batch(3, 15, seed=11, shapes="full")  # (test_ipm_wave_host.py's smallest pattern)
+
+
+@pytest.fixture(scope="module")
+def family_sources():
+    """The generated source of each module family: one lane and lane groups of 8 (farmer, 64
+    scenarios), and both workgroup kernels on a small block-arrow pattern."""
+    import mpisppy_amd._lib as L
+    keep = os.environ.get("PHGPU_IPM_BLK")
+    out = {"lane1": (L.ipm_source(_farmer(64))[0], "k_solve_ipm"), "lanes8": (L.ipm_source(_farmer(64), 8)[0], "k_solve_ipm_ml")}
+    try:
+        for name, blk in (("k_solve_ipm_blk", "1"), ("k_solve_ipm_wave", "0")):
+            os.environ["PHGPU_IPM_BLK"] = blk
+            out[name] = (L.ipm_source(_wg_batch(), 64)[0], name)
+    finally:
+        if keep is None:
+            os.environ.pop("PHGPU_IPM_BLK", None)
+        else:
+            os.environ["PHGPU_IPM_BLK"] = keep
+    return out
+
+
+# what a path-6 module holds exactly once: the argument blocks (ipm_args.h), the statistics
+# roll and the tunables' defaults (jit_ipm_common.hip.in)
+ONCE = ["struct ph_step {", "struct ipmw_params ", "struct ipm_step_params ", "struct ipm_params ",
+        "void ipm_stats_roll(", "#define IPM_SIG_MAX"]
+
+
+@pytest.mark.parametrize("family", ["lane1", "lanes8", "k_solve_ipm_blk", "k_solve_ipm_wave"])
+def test_shared_definitions_occur_once(family_sources, family):
+    src, kernel = family_sources[family]
+    assert kernel in src
+    for text in ONCE:
+        assert src.count(text) == 1, (family, text, src.count(text))
+    # the argument blocks and the shared defaults follow the preamble's first line (the host
+    # emulation cuts the source there) and the tuning, and precede the kernel template
+    gam = src.index("#define IPM_GAM")
+    assert gam < src.index("struct ph_step {") < src.index("#define IPM_SIG_MAX") < src.index('extern "C" __global__', gam)
+    # path 5 (the fallback of the small families): its argument block once, ahead of its kernel
+    assert src.count("struct jit_params {") == (1 if family in ("lane1", "lanes8") else 0)
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
+@pytest.mark.parametrize("family", ["lanes8", "k_solve_ipm_blk", "k_solve_ipm_wave"])
+def test_family_modules_compile_for_gfx950(family_sources, family, tmp_path):
+    """(the one-lane farmer module: test_generated_module_compiles_for_gfx950_without_scratch)"""
+    src, kernel = family_sources[family]
+    p = tmp_path / "ipm.hip"
+    p.write_text("#include <hip/hip_runtime.h>\n" + src)
+    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "--cuda-device-only",
+                        "-Rpass-analysis=kernel-resource-usage", "-o", str(tmp_path / "x.o"), str(p)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert f"Function Name: {kernel} " in r.stderr, r.stderr[-2000:]
+
+
 def test_host_kernel_farmer_iter0_and_prox_vs_oracle():
     from mpisppy_amd.examples import farmer
     from oracle import farmer_vec as FV

@@ -273,6 +273,65 @@ int phgpu_ph_step_defer(phgpu_handle h, const double* x, double* node_buf, doubl
 /* Run a step deferred by phgpu_ph_step_defer now (no-op if none is pending). */
 int phgpu_ph_step_flush(phgpu_handle h);
 
+/* Adaptive rho (mpisppy/extensions/norm_rho_updater.py) and the residual sums of the
+ * primal-dual and norm-rho convergers (mpisppy/convergers/), in two calls with the ranks'
+ * sum of `planes` by the caller between them.  Both are ordered on the stream and do not
+ * synchronise (the first use allocates their own workspace; phgpu_workspace_bytes grows
+ * only then); both work on a PHGPU_SHARED_MATRIX handle.
+ *
+ * phgpu_ph_residuals: one pass over the local scenarios.  planes[4 * num_nodes * nlen_max],
+ * four node-indexed planes laid out like one half of node_buf ([g * nlen_max + off]), the
+ * sums over the local scenarios whose node at the nonant's depth is g of
+ *   plane 0   prob_s |x - x̄|    prob_s the scenario's unconditional probability (not
+ *             prob_coeff, with variable probabilities too): the primal residual of
+ *             NormRhoUpdater._compute_primal_residual_norm, norm_rho_updater.py:73-83
+ *             (its Allreduce, :85-89, is the caller's sum)
+ *   plane 1   pcoef |x - x̄|     pcoef = prob_coeff, or pvar[k, s] with variable
+ *             probabilities: summed over its entries, PrimalDualConverger's primal gap,
+ *             primal_dual_converger.py:66-82
+ *   plane 2   rho[k, s]          unweighted: sum of plane 2 x |x̄ - x̄_prev| is the
+ *             converger's dual gap, primal_dual_converger.py:96-107
+ *   plane 3   prob_s rho[k, s]   summed over its entries, NormRhoConverger's rho norm,
+ *             norm_rho_converger.py:26
+ * rho_last[num_nodes * nlen_max] (same indexing; rank-local, never summed over ranks):
+ * rho[k, s] of the last local scenario (highest local index) of node g.
+ * _compute_dual_residual_norm (norm_rho_updater.py:98-104) overwrites dual_resid[ndn_i]
+ * scenario by scenario, so every rank's dual residual carries the rho of its own last
+ * scenario at the node; it is taken here because phgpu_norm_rho_update rewrites rho.
+ *   x[n*S], xbar[nn*S], rho[nn*S]: device, read.  Both outputs are overwritten in full
+ *   (entries no local scenario reaches are 0).
+ * Wave-uniform nodes are summed deterministically (per-wave partials, then an ordered
+ * final sum, as phgpu_ph_reduce); a wave that spans nodes adds by fp64 atomics. */
+int phgpu_ph_residuals(phgpu_handle h, const double* x, const double* xbar, const double* rho,
+                       double* planes, double* rho_last, void* stream);
+
+/* Constants of the rho rule (NormRhoUpdater's options, norm_rho_updater.py:12-31). */
+typedef struct {
+    double tol;              /* convergence_tolerance                              [1e-4] */
+    double inc;              /* rho_increase_multiplier                            [2.0] */
+    double dec;              /* rho_decrease_multiplier                            [2.0] */
+    double conv_dec;         /* rho_converged_decrease_multiplier                  [1.1] */
+    double f;                /* primal_dual_difference_factor                      [100.0] */
+    int32_t allow_decrease;  /* the host's ph_iter >= iterations_converged_before_decrease */
+} phgpu_norm_rho_params;
+
+/* The rule of NormRhoUpdater.miditer (norm_rho_updater.py:128-143) for every local (k, s),
+ * after the ranks' sum of planes.  With g the scenario's node at k's depth:
+ *   p = planes[g * nlen_max + off]                                  (plane 0)
+ *   d = rho_last[g * nlen_max + off] * |xbar_node[..] - xbar_prev[..]|
+ *   if p > f d and p > tol:         rho[k, s] *= inc
+ *   else if d > f p and d > tol:    rho[k, s] /= dec   only if allow_decrease
+ *   else if p < tol and d < tol:    rho[k, s] /= conv_dec
+ * (strict comparisons, as the reference; a decrease that is not allowed takes no action and
+ * does not fall through to the third test).
+ *   xbar_node: the first half of the reduced node_buf; xbar_prev: the caller's copy of it
+ *   from the previous miditer (_prev_avg, norm_rho_updater.py:50-53); rho: device [nn*S],
+ *   rewritten in place; counts: device int64[4] or NULL, the local (k, s) entries that took
+ *   no action / increased / decreased / took the converged decrease. */
+int phgpu_norm_rho_update(phgpu_handle h, const phgpu_norm_rho_params* prm, const double* planes,
+                          const double* rho_last, const double* xbar_node, const double* xbar_prev,
+                          double* rho, int64_t* counts, void* stream);
+
 /* Local probability-weighted sums (spopt.py:310-439) into out[5]:
  *   out[0] = sum_s prob_s * obj_s    out[1] = sum_s prob_s * bound_s
  *   out[2] = sum_s prob_s (E1)       out[3] = sum_{s feasible} prob_s, where feasible

@@ -14,6 +14,9 @@
 //   PH objective terms                  phbase.py:617-699
 //   _Compute_Xbar / Update_W / conv     phbase.py:27-107, 293-343
 //   Ebound / Eobjective / E1 / feas     spopt.py:310-439
+//   NormRhoUpdater residuals and rule   extensions/norm_rho_updater.py:55-143
+//   converger sums                      convergers/primal_dual_converger.py:58-110,
+//                                       convergers/norm_rho_converger.py:23-29
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -222,6 +225,11 @@ struct phgpu_state {
     int fuse_now;      // ipm_launch folds pend into this launch
     int64_t folded;    // PH steps folded into solve launches so far (phgpu_ipm_info)
     int32_t* nb_idx;   // [nn] node_buf index (node of the local scenarios, offset) of nonant k (two-stage)
+    // phgpu_ph_residuals' own per-wave partials [nwaves * nn * 4] and node tags [nwaves * nn],
+    // allocated at its first call (part / part_node may belong to a deferred step or to the
+    // path-6 epilogue)
+    double* rs_part;
+    int32_t* rs_node;
 };
 
 #define IX(k) ((size_t)(k) * (size_t)S + (size_t)s)
@@ -1196,6 +1204,251 @@ __global__ void __launch_bounds__(XF_THREADS) k_xbar_final(phgpu_state st, doubl
         }
         atomicAdd(&node_buf[g * st.nlen_max + off], sa);
         atomicAdd(&node_buf[half + g * st.nlen_max + off], sb);
+    }
+}
+
+// ------------------------------------------------------------------ adaptive rho
+// The residual sums of NormRhoUpdater and the two convergers (include/phgpu.h
+// phgpu_ph_residuals) by the scheme of k_xbar_partial / k_xbar_final, with four values per
+// (wave, nonant) in partials of their own (st.rs_part / st.rs_node).
+#define RS_NV 4  // planes: prob |x - x̄|, pcoef |x - x̄|, rho, prob rho
+
+// both outputs of phgpu_ph_residuals to 0 (entries no local scenario reaches stay 0)
+__global__ void __launch_bounds__(256) k_resid_clear(double* __restrict__ planes, int64_t np,
+                                                     double* __restrict__ rho_last, int64_t nl) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < np + nl; i += stride) {
+        if (i < np) planes[i] = 0.0;
+        else rho_last[i - np] = 0.0;
+    }
+}
+
+// norm_rho_updater.py:73-83 (plane 0), primal_dual_converger.py:66-82 and 96-107 (planes 1,
+// 2), norm_rho_converger.py:26 (plane 3): per-wave partial sums, one nonant per grid row; a
+// wave whose scenarios share one node writes one partial (deterministic), a mixed wave adds
+// per lane with fp64 atomics.  rho_last (norm_rho_updater.py:98-104, the last local
+// scenario's rho at each node): the local scenarios are in tree order, so a node's scenarios
+// are one run, and the lane at the end of a run stores its rho.
+__global__ void __launch_bounds__(BLOCK)
+k_resid_partial(phgpu_state st, const double* __restrict__ x, const double* __restrict__ xbar,
+                const double* __restrict__ rho, double* __restrict__ planes, double* __restrict__ rho_last) {
+    const int64_t S = st.S;
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t wave = s / WAVE;
+    const bool act = s < S;
+    const int half = st.num_nodes * st.nlen_max;
+    const int k = blockIdx.y;
+    if (k >= st.nn) return;
+    const int d = st.nonant_depth[k];
+    const int gnode = act ? st.node_of[IX(d)] : -1;
+    const int gnext = (act && s + 1 < S) ? st.node_of[IX(d) + 1] : -1;
+    const double r = act ? rho[IX(k)] : 0.0;
+    const double ad = act ? fabs(x[IX(st.nonant_col[k])] - xbar[IX(k)]) : 0.0;
+    const double pi = act ? st.prob[s] : 0.0;
+    const double pc = act ? (st.pvar ? st.pvar[IX(k)] : st.pcoef[IX(d)]) : 0.0;
+    double v[RS_NV] = {pi * ad, pc * ad, r, pi * r};
+    if (act && gnext != gnode) rho_last[gnode * st.nlen_max + st.nonant_off[k]] = r;
+    const int g0 = __shfl(gnode, 0, WAVE);
+    const bool uniform = !__any(act && gnode != g0);
+    if (uniform) {
+#pragma unroll
+        for (int j = 0; j < RS_NV; ++j) v[j] = wave_sum(v[j]);
+        if ((threadIdx.x & (WAVE - 1)) == 0) {
+#pragma unroll
+            for (int j = 0; j < RS_NV; ++j) st.rs_part[(wave * st.nn + k) * RS_NV + j] = v[j];
+            st.rs_node[wave * st.nn + k] = g0;
+        }
+    } else {
+        if (act) {
+            const int o = gnode * st.nlen_max + st.nonant_off[k];
+#pragma unroll
+            for (int j = 0; j < RS_NV; ++j) atomicAdd(&planes[(int64_t)j * half + o], v[j]);
+        }
+        if ((threadIdx.x & (WAVE - 1)) == 0) st.rs_node[wave * st.nn + k] = -1;
+    }
+}
+
+// k_xbar_final for the four residual values: ordered segmented sum of the per-wave partials,
+// one block per nonant, into the cleared planes.  A run (one node's consecutive waves) inside
+// one thread's chunk is flushed by that thread; a run that crosses chunks is flushed once, by
+// the thread where it starts, which adds the following chunks' pieces in thread order; a
+// nonant whose waves all share one node takes the fixed-order tree sum.
+// assign: the planes were not cleared (one tree node, every entry is some nonant's): the
+// fixed-order sum is stored, not added (as k_xbar_final's assign).
+__global__ void __launch_bounds__(XF_THREADS) k_resid_final(phgpu_state st, double* __restrict__ planes, int assign) {
+    __shared__ int fnode[XF_THREADS], lnode[XF_THREADS];
+    __shared__ double fv[RS_NV][XF_THREADS], lv[RS_NV][XF_THREADS];
+    __shared__ int single;
+    const int k = blockIdx.x;
+    const int t = threadIdx.x;
+    const int64_t half = (int64_t)st.num_nodes * st.nlen_max;
+    const int off = st.nonant_off[k];
+    const int64_t nw = st.nwaves;
+    const int64_t C = (nw + XF_THREADS - 1) / XF_THREADS;
+    const int64_t w0 = (int64_t)t * C, w1 = (w0 + C < nw) ? w0 + C : nw;
+    int cur = -1, first = -1;
+    double a[RS_NV] = {0.0, 0.0, 0.0, 0.0}, a_first[RS_NV] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t w = w0; w < w1; ++w) {
+        const int gnode = st.rs_node[w * st.nn + k];
+        double p[RS_NV];
+#pragma unroll
+        for (int j = 0; j < RS_NV; ++j) p[j] = st.rs_part[(w * st.nn + k) * RS_NV + j];
+        if (gnode < 0) continue;
+        if (gnode != cur) {
+            if (cur >= 0) {
+                if (first < 0) {  // close the chunk's first run
+                    first = cur;
+#pragma unroll
+                    for (int j = 0; j < RS_NV; ++j) a_first[j] = a[j];
+                } else {          // a complete middle run
+#pragma unroll
+                    for (int j = 0; j < RS_NV; ++j) atomicAdd(&planes[j * half + cur * st.nlen_max + off], a[j]);
+                }
+            }
+            cur = gnode;
+#pragma unroll
+            for (int j = 0; j < RS_NV; ++j) a[j] = 0.0;
+        }
+#pragma unroll
+        for (int j = 0; j < RS_NV; ++j) a[j] += p[j];
+    }
+    if (t == 0) single = 1;
+    if (first < 0) {  // zero or one run in this chunk: it is the first (and last) run
+        fnode[t] = cur;
+        lnode[t] = -1;
+#pragma unroll
+        for (int j = 0; j < RS_NV; ++j) {
+            fv[j][t] = a[j];
+            lv[j][t] = 0.0;
+        }
+    } else {
+        fnode[t] = first;
+        lnode[t] = cur;
+#pragma unroll
+        for (int j = 0; j < RS_NV; ++j) {
+            fv[j][t] = a_first[j];
+            lv[j][t] = a[j];
+        }
+    }
+    __syncthreads();
+    {
+        const int g0 = fnode[0] >= 0 ? fnode[0] : lnode[0];
+        if ((fnode[t] >= 0 && fnode[t] != g0) || (lnode[t] >= 0 && lnode[t] != g0)) single = 0;
+    }
+    __syncthreads();
+    if (single) {
+#pragma unroll
+        for (int j = 0; j < RS_NV; ++j) fv[j][t] += lv[j][t];
+        __syncthreads();
+        for (int o = XF_THREADS / 2; o > 0; o >>= 1) {
+            if (t < o) {
+#pragma unroll
+                for (int j = 0; j < RS_NV; ++j) fv[j][t] += fv[j][t + o];
+            }
+            __syncthreads();
+        }
+        if (t == 0) {
+            int g0 = -1;
+            for (int u = 0; u < XF_THREADS && g0 < 0; ++u) g0 = fnode[u] >= 0 ? fnode[u] : lnode[u];
+            if (g0 >= 0) {
+#pragma unroll
+                for (int j = 0; j < RS_NV; ++j) {
+                    double* q = &planes[j * half + g0 * st.nlen_max + off];
+                    *q = assign ? fv[j][0] : *q + fv[j][0];
+                }
+            }
+        }
+        return;
+    }
+    // (lnode[u] >= 0 implies fnode[u] >= 0: a chunk's runs are maximal and distinct.)
+    for (int side = 0; side < 2; ++side) {
+        const int g = side ? lnode[t] : fnode[t];
+        if (g < 0) continue;
+        if (side == 0) {  // does the first run continue the previous non-empty chunk's tail?
+            int p = t - 1;
+            while (p >= 0 && fnode[p] < 0) --p;
+            if (p >= 0 && (lnode[p] >= 0 ? lnode[p] : fnode[p]) == g) continue;
+        }
+        double sv[RS_NV];
+#pragma unroll
+        for (int j = 0; j < RS_NV; ++j) sv[j] = side ? lv[j][t] : fv[j][t];
+        if (side == 1 || lnode[t] < 0) {  // this run reaches the end of the chunk
+            for (int u = t + 1; u < XF_THREADS; ++u) {
+                if (fnode[u] < 0) continue;  // empty chunk
+                if (fnode[u] != g) break;
+#pragma unroll
+                for (int j = 0; j < RS_NV; ++j) sv[j] += fv[j][u];
+                if (lnode[u] >= 0) break;    // the run ends inside chunk u
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < RS_NV; ++j) atomicAdd(&planes[j * half + g * st.nlen_max + off], sv[j]);
+    }
+}
+
+// NormRhoUpdater.miditer's rule (norm_rho_updater.py:128-143) for every local (k, s): one
+// nonant per grid row, a row's blocks stride over the scenarios (the grid of k_ph_update).
+// The residuals are per (node, nonant), so every rank and every scenario of a node takes the
+// same branch.  counts (may be null): entries that took no action / increase / decrease /
+// converged decrease, by integer atomics (one per wave and action).
+#define NR_T 256
+#define NR_U 4
+__global__ void __launch_bounds__(NR_T)
+k_norm_rho_update(phgpu_state st, phgpu_norm_rho_params prm, const double* __restrict__ plane0,
+                  const double* __restrict__ rho_last, const double* __restrict__ xbar_node,
+                  const double* __restrict__ xbar_prev, double* __restrict__ rho,
+                  unsigned long long* __restrict__ counts) {
+    const int64_t S = st.S;
+    const int k = blockIdx.y;
+    int c[4] = {0, 0, 0, 0};
+    if (k < st.nn) {
+        const int d = st.nonant_depth[k];
+        const int off = st.nonant_off[k], nl = st.nlen_max;
+        const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+        for (int64_t s0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s0 < S; s0 += NR_U * stride) {
+            double p[NR_U], dr[NR_U], r[NR_U];
+#pragma unroll
+            for (int u = 0; u < NR_U; ++u) {
+                const int64_t s = s0 + u * stride;
+                p[u] = dr[u] = r[u] = 0.0;
+                if (s < S) {
+                    const int o = st.node_of[(int64_t)d * S + s] * nl + off;
+                    p[u] = plane0[o];
+                    dr[u] = rho_last[o] * fabs(xbar_node[o] - xbar_prev[o]);
+                    r[u] = rho[(int64_t)k * S + s];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < NR_U; ++u) {
+                const int64_t s = s0 + u * stride;
+                if (s < S) {
+                    int act = 0;
+                    if (p[u] > prm.f * dr[u] && p[u] > prm.tol) {
+                        act = 1;
+                        rho[(int64_t)k * S + s] = r[u] * prm.inc;
+                    } else if (dr[u] > prm.f * p[u] && dr[u] > prm.tol) {
+                        if (prm.allow_decrease) {
+                            act = 2;
+                            rho[(int64_t)k * S + s] = r[u] / prm.dec;
+                        }
+                    } else if (p[u] < prm.tol && dr[u] < prm.tol) {
+                        act = 3;
+                        rho[(int64_t)k * S + s] = r[u] / prm.conv_dec;
+                    }
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) c[a] += act == a;
+                }
+            }
+        }
+    }
+    if (counts) {
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            int v = c[a];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, WAVE);
+            if ((threadIdx.x & (WAVE - 1)) == 0 && v) atomicAdd(&counts[a], (unsigned long long)v);
+        }
     }
 }
 
@@ -3357,6 +3610,58 @@ static int step_local_impl(phgpu_state* h, const double* x, double* node_buf, do
     return 0;
 }
 
+// norm_rho_updater.py:55-104 and the convergers' sums (include/phgpu.h)
+extern "C" int phgpu_ph_residuals(phgpu_handle h, const double* x, const double* xbar, const double* rho,
+                                  double* planes, double* rho_last, void* stream) {
+    if (!h || !x || !xbar || !rho || !planes || !rho_last) return set_err(-1, "null argument");
+    FLUSH_STEP(h);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t half = (int64_t)h->num_nodes * h->nlen_max;
+    // one tree node whose every entry is a nonant's (two-stage problems): every wave is
+    // uniform, so the final sums are stored and the last scenario's lane stores rho_last --
+    // both outputs are overwritten in full without a clearing launch
+    const int assign = (h->num_nodes == 1 && h->nlen_max == h->nn) ? 1 : 0;
+    if (!assign) {
+        hipLaunchKernelGGL(k_resid_clear, dim3((unsigned)std::min<int64_t>((5 * half + 255) / 256, 256)), dim3(256), 0,
+                           st, planes, (int64_t)RS_NV * half, rho_last, half);
+        HIPCHK(hipGetLastError());
+    }
+    if (h->nn == 0) return 0;
+    if (!h->rs_part) {  // first use: workspace of its own (not part / part_node)
+        const size_t cnt = (size_t)h->nwaves * (size_t)h->nn;
+        int rc = dalloc(h, &h->rs_part, cnt * RS_NV);
+        if (!rc) rc = dalloc(h, &h->rs_node, cnt);
+        if (rc) {
+            if (h->rs_part) (void)hipFree(h->rs_part);
+            h->rs_part = nullptr;
+            return rc;
+        }
+    }
+    dim3 g = grid_for(h->S);
+    g.y = (unsigned)h->nn;
+    hipLaunchKernelGGL(k_resid_partial, g, dim3(BLOCK), 0, st, *h, x, xbar, rho, planes, rho_last);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_resid_final, dim3(h->nn), dim3(XF_THREADS), 0, st, *h, planes, assign);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// norm_rho_updater.py:128-143
+extern "C" int phgpu_norm_rho_update(phgpu_handle h, const phgpu_norm_rho_params* prm, const double* planes,
+                                     const double* rho_last, const double* xbar_node, const double* xbar_prev,
+                                     double* rho, int64_t* counts, void* stream) {
+    if (!h || !prm || !planes || !rho_last || !xbar_node || !xbar_prev || !rho) return set_err(-1, "null argument");
+    FLUSH_STEP(h);
+    hipStream_t st = (hipStream_t)stream;
+    if (counts) HIPCHK(hipMemsetAsync(counts, 0, 4 * sizeof(int64_t), st));
+    if (h->nn == 0) return 0;
+    const int64_t bx = std::min<int64_t>((h->S + NR_T - 1) / NR_T, std::max<int64_t>(1, UPD_BLOCKS / h->nn));
+    hipLaunchKernelGGL(k_norm_rho_update, dim3((unsigned)bx, (unsigned)h->nn), dim3(NR_T), 0, st, *h, *prm, planes,
+                       rho_last, xbar_node, xbar_prev, rho, (unsigned long long*)counts);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 extern "C" int phgpu_expectations(phgpu_handle h, const double* obj, const double* bound,
                                   const int32_t* status, double* out, void* stream) {
     if (!h || !obj || !bound || !status || !out) return set_err(-1, "null argument");
@@ -3439,7 +3744,7 @@ extern "C" int phgpu_destroy(phgpu_handle h) {
     if (h->stats_gen) (void)hipFree(h->stats_gen);
     {
         void* more[] = {h->xp[0], h->xp[1], h->xp_node[0], h->xp_node[1], h->xp_dirty[0], h->xp_dirty[1],
-                        h->cpart_blk, h->blk_cnt, h->nb_idx};
+                        h->cpart_blk, h->blk_cnt, h->nb_idx, h->rs_part, h->rs_node};
         for (void* p : more)
             if (p) (void)hipFree(p);
     }

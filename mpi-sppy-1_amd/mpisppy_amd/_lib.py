@@ -40,6 +40,18 @@ class PhgpuOptions(ctypes.Structure):
     ]
 
 
+class NormRhoParams(ctypes.Structure):
+    """phgpu_norm_rho_params (include/phgpu.h): the constants of NormRhoUpdater's rule."""
+    _fields_ = [
+        ("tol", c_dbl),
+        ("inc", c_dbl),
+        ("dec", c_dbl),
+        ("conv_dec", c_dbl),
+        ("f", c_dbl),
+        ("allow_decrease", c_i32),
+    ]
+
+
 OPTIMAL, ITER_LIMIT, PRIMAL_INFEASIBLE, DUAL_INFEASIBLE = 0, 1, 2, 3
 SHARED_MATRIX = 1          # phgpu_create2 flag (include/phgpu.h)
 
@@ -52,7 +64,7 @@ EXPORTS = ["phgpu_default_options", "phgpu_create", "phgpu_create2", "phgpu_set_
            "phgpu_ph_update_ex", "phgpu_ph_step_local", "phgpu_ph_step_defer", "phgpu_ph_step_flush",
            "phgpu_set_nonant_probs", "phgpu_set_ipm_tuning", "phgpu_ipm_prof",
            "phgpu_ph_loop", "phgpu_stream_info", "phgpu_comm_unique_id", "phgpu_comm_init",
-           "phgpu_allreduce_sum"]
+           "phgpu_allreduce_sum", "phgpu_ph_residuals", "phgpu_norm_rho_update"]
 
 _lib = None
 
@@ -101,6 +113,9 @@ def load(path=None):
     lib.phgpu_comm_unique_id.argtypes = [ctypes.c_char_p]
     lib.phgpu_comm_init.argtypes = [c_vp, ctypes.c_char_p, c_int, c_int, c_int]
     lib.phgpu_allreduce_sum.argtypes = [c_vp, c_int, c_vp, c_i64, c_vp]
+    lib.phgpu_ph_residuals.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
+    lib.phgpu_norm_rho_update.argtypes = [c_vp, ctypes.POINTER(NormRhoParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                          c_vp]
     lib.phgpu_ipm_info.argtypes = [c_vp, ctypes.POINTER(c_dbl)]
     lib.phgpu_ipm_prof.argtypes = [c_vp, ctypes.POINTER(ctypes.c_ulonglong), c_i64]
     lib.phgpu_ipm_prof.restype = c_i64

@@ -7,6 +7,8 @@ GPU, scenario-fastest ``[k, S]``) and sequences the per-PH-iteration work:
     Compute_Xbar    -> phgpu_ph_reduce + all-reduce    (phbase.py:27-107)
     Update_W + conv -> phgpu_ph_update + all-reduce    (phbase.py:293-343)
     Ebound/Eobj/E1  -> phgpu_expectations + all-reduce (spopt.py:310-439)
+    adaptive rho    -> phgpu_ph_residuals + all-reduce + phgpu_norm_rho_update
+                                                       (extensions/norm_rho_updater.py:55-143)
 
 All launches go to torch's current stream; host synchronisation happens only where
 the reference needs a host scalar (the convergence test, bounds).
@@ -124,7 +126,8 @@ class PHEngine:
         # library calls of the PH step, by kind (tests assert which path a loop took)
         self.calls = {"ph_reduce": 0, "ph_update_ex": 0, "ph_step_local": 0, "ph_step_defer": 0,
                       "allreduce_xbar": 0, "allreduce_conv_side": 0, "allreduce_conv_main": 0, "xbar_ahead_used": 0,
-                      "ph_loop": 0}
+                      "ph_loop": 0, "ph_residuals": 0, "norm_rho_update": 0, "allreduce_resid": 0,
+                      "solve_deferred": 0}
         # several ranks: the conv all-reduce on a side stream under the next solve (False: on
         # the launch stream ahead of it -- bench.py --no-conv-overlap, the comparison case)
         self.overlap_conv = True
@@ -484,6 +487,7 @@ class PHEngine:
         self._launch_id += 1
         if speculative:
             self._spec_id = self._launch_id
+            self.calls["solve_deferred"] += 1
         else:
             self._cur_id = self._launch_id
         self._step_deferred = False   # the library folds a deferred step into this launch or runs it first
@@ -672,6 +676,82 @@ class PHEngine:
         _lib.check(self.lib.phgpu_ph_update_ex(self.h, _ptr(self.x), _ptr(self.node_buf), _ptr(self.xbar),
                                                _ptr(self.W), _ptr(self.rho), 1 if update_W else 0,
                                                _ptr(conv), _ptr(stats), self._stream()), "phgpu_ph_update_ex")
+
+    # -------------------------------------------------------------- adaptive rho
+    def _resid_bufs(self):
+        if getattr(self, "resid", None) is None:
+            half = self.num_nodes * self.nlen_max
+            self.resid = torch.zeros(4 * half, dtype=torch.float64, device=self.device)
+            self.rho_last = torch.zeros(half, dtype=torch.float64, device=self.device)
+            self.nr_counts = torch.zeros(4, dtype=torch.int64, device=self.device)
+            self._xbar_prev = None
+        return self.num_nodes * self.nlen_max
+
+    def residuals(self):
+        """The residual sums of NormRhoUpdater and the convergers (phgpu_ph_residuals;
+        norm_rho_updater.py:55-104, primal_dual_converger.py:58-110, norm_rho_converger.py:23-29)
+        for the current x, x̄ and rho: four node-indexed planes in ``resid`` (summed over the
+        ranks: the reference's per-node and ROOT Allreduces in one) and this rank's
+        ``rho_last``.  Device work only."""
+        self._flush_xbar()
+        self._resid_bufs()
+        self.calls["ph_residuals"] += 1
+        _lib.check(self.lib.phgpu_ph_residuals(self.h, _ptr(self.x), _ptr(self.xbar), _ptr(self.rho),
+                                               _ptr(self.resid), _ptr(self.rho_last), self._stream()),
+                   "phgpu_ph_residuals")
+        if self.comm.size > 1:
+            self.calls["allreduce_resid"] += 1
+            self._allreduce_sum_(self.resid)
+        return self.resid
+
+    def xbar_snapshot(self):
+        """Keep the node x̄ of the last update as the previous average of the next rho update
+        (NormRhoUpdater._snapshot_avg, norm_rho_updater.py:50-53): a device copy."""
+        self._flush_xbar()
+        half = self._resid_bufs()
+        if self._xbar_prev is None:
+            self._xbar_prev = torch.empty(half, dtype=torch.float64, device=self.device)
+        self._xbar_prev.copy_(self.node_buf[:half])
+
+    def norm_rho_update(self, params):
+        """NormRhoUpdater.miditer's rule on the device (phgpu_norm_rho_update,
+        norm_rho_updater.py:128-143) from the planes ``residuals`` left and the x̄ snapshot,
+        which is then renewed (:124).  ``params``: _lib.NormRhoParams."""
+        if getattr(self, "_xbar_prev", None) is None or getattr(self, "resid", None) is None:
+            raise _lib.PhgpuError("norm_rho_update needs residuals() and an earlier xbar_snapshot()")
+        self.calls["norm_rho_update"] += 1
+        _lib.check(self.lib.phgpu_norm_rho_update(self.h, ctypes.byref(params), _ptr(self.resid),
+                                                  _ptr(self.rho_last), _ptr(self.node_buf), _ptr(self._xbar_prev),
+                                                  _ptr(self.rho), _ptr(self.nr_counts), self._stream()),
+                   "phgpu_norm_rho_update")
+        self.xbar_snapshot()
+
+    def norm_rho_counts(self):
+        """Local (k, s) entries of the last rho update that took no action / increased /
+        decreased / took the converged decrease (one small read back)."""
+        return self.nr_counts.cpu().numpy()
+
+    def residual_planes(self):
+        """Host [4, num_nodes * nlen_max] copy of the planes of the last ``residuals``."""
+        return self.resid.cpu().numpy().reshape(4, -1)
+
+    def node_xbar_flat(self):
+        """Host copy of the node x̄ (first half of node_buf), [num_nodes * nlen_max]."""
+        self._flush_xbar()
+        return self.node_buf[:self.num_nodes * self.nlen_max].cpu().numpy()
+
+    def primal_gap(self):
+        """PrimalDualConverger._compute_primal_convergence (primal_dual_converger.py:58-85)."""
+        return float(self.residual_planes()[1].sum())
+
+    def dual_gap(self, xbar_prev):
+        """PrimalDualConverger._compute_dual_residual (primal_dual_converger.py:87-110);
+        ``xbar_prev``: host node x̄ of the previous test (``node_xbar_flat``)."""
+        return float((self.residual_planes()[2] * np.abs(self.node_xbar_flat() - xbar_prev)).sum())
+
+    def rho_norm(self):
+        """NormRhoConverger._compute_rho_norm (norm_rho_converger.py:23-29)."""
+        return float(self.residual_planes()[3].sum())
 
     def convergence_diff(self):
         """phbase.py:330-343: sum over ranks of per-rank means, / n_proc (host float)."""

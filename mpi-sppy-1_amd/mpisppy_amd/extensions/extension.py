@@ -15,6 +15,11 @@ defines, so the others cost nothing.
 class Extension:
     """Base class: every hook is a no-op; ``self.opt`` is the SPOpt/PHBase object."""
 
+    # True when ``miditer`` only enqueues device work that depends on the iteration count
+    # and never on the convergence value: PHBase.iterk_loop then calls it right after
+    # Update_W and keeps its speculative solve (no reference counterpart)
+    miditer_on_device = False
+
     def __init__(self, spopt_object):
         self.opt = spopt_object
 
@@ -63,6 +68,12 @@ class MultiExtension(Extension):
     def __init__(self, ph, ext_classes):
         super().__init__(ph)
         self.extdict = {cls.__name__: cls(ph) for cls in ext_classes}
+
+    @property
+    def miditer_on_device(self):
+        """True only if every member that overrides ``miditer`` keeps it on the device."""
+        mid = [e for e in self.extdict.values() if overrides(e, "miditer")]
+        return bool(mid) and all(e.miditer_on_device for e in mid)
 
     def pre_solve(self, subproblem):
         for e in self.extdict.values():

@@ -277,10 +277,21 @@ class PHBase(SPOpt):
             # path 4 keeps one warm-start slot (phgpu_solve_deferred is rejected), and its
             # solves take seconds, against the ~0.05 ms a speculative launch hides
             return False
-        if have_ext and any(overrides(self.extobject, h) for h in ("miditer", "pre_solve_loop", "post_solve_loop",
+        if have_ext and any(overrides(self.extobject, h) for h in ("pre_solve_loop", "post_solve_loop",
                                                                     "pre_solve", "post_solve")):
             return False
+        if have_ext and overrides(self.extobject, "miditer") and not self._miditer_early(have_ext):
+            return False
         return True
+
+    def _miditer_early(self, have_ext):
+        """True when the extension's miditer only enqueues device work that does not depend
+        on conv (Extension.miditer_on_device, e.g. NormRhoUpdater): the speculative loop then
+        calls it right after Update_W, ahead of the speculative solve and of the conv
+        readback.  The reference runs miditer before the break test (phbase.py:919-926), so
+        it runs whether or not the loop stops, there as here."""
+        return bool(have_ext and overrides(self.extobject, "miditer")
+                    and getattr(self.extobject, "miditer_on_device", False))
 
     def _fused_loop(self, have_ext):
         """The whole loop in one launch (engine.ph_loop) when nothing but the
@@ -345,12 +356,18 @@ class PHBase(SPOpt):
             # extension could change the problem between the test and the solve.  With it,
             # one rank's x̄ / W / conv step runs in the solve launch itself.
             spec = self._speculate(have_ext)
+            # a device-side miditer (the rho update) reads W's inputs x̄ and x and rewrites
+            # rho between Update_W and the solve: the step is then not deferred into the
+            # solve launch, and miditer runs here instead of after the conv readback
+            mid_early = spec and self._miditer_early(have_ext)
             self.Compute_Xbar(verbose)
-            self._defer_update = spec
+            self._defer_update = spec and not mid_early
             try:
                 self.Update_W(verbose)
             finally:
                 self._defer_update = False
+            if mid_early:
+                self.extobject.miditer()
             if spec:
                 # (several ranks: the update is marked, the solve launched, then the conv
                 # all-reduce issued on the side stream behind the mark)
@@ -364,7 +381,7 @@ class PHBase(SPOpt):
             else:
                 self.conv = self.convergence_diff()
             self.gripe_report()                        # the previous iteration's solves
-            if have_ext and hasattr(self.extobject, "miditer"):
+            if have_ext and hasattr(self.extobject, "miditer") and not mid_early:
                 self.extobject.miditer()
             if self.ph_converger is not None:
                 if self.convobject.is_converged():

@@ -11,7 +11,10 @@ import copy
 from ..cylinders.hub import PHHub
 from ..cylinders.lagrangian_bounder import LagrangianOuterBound
 from ..cylinders.xhatshufflelooper_bounder import XhatShuffleInnerBound
+from ..convergers.norm_rho_converger import NormRhoConverger
+from ..convergers.primal_dual_converger import PrimalDualConverger
 from ..extensions.extension import MultiExtension
+from ..extensions.norm_rho_updater import NormRhoUpdater
 from ..opt.ph import PH
 from ..phbase import PHBase
 from .xhat_eval import Xhat_Eval
@@ -136,6 +139,42 @@ def extension_adder(hub_dict, ext_class):
     elif ok["extensions"] != ext_class:
         ok["extension_kwargs"] = {"ext_classes": [ok["extensions"], ext_class]}
         ok["extensions"] = MultiExtension
+    return hub_dict
+
+
+# examples/farmer/farmer_cylinders.py:67-75 (farmer_rho_demo.py:80-84): the converger class
+# the flags ask for
+def converger_from_cfg(cfg):
+    if _get(cfg, "use_norm_rho_converger", False):
+        if not _get(cfg, "use_norm_rho_updater", False):
+            raise RuntimeError("--use-norm-rho-converger requires --use-norm-rho-updater")
+        return NormRhoConverger
+    if _get(cfg, "primal_dual_converger", False):
+        return PrimalDualConverger
+    return None
+
+
+# examples/farmer/farmer_cylinders.py:110-113 (cfg.use_norm_rho_updater).  The reference
+# scripts hard-wire {'verbose': True}; here the table is printed only when
+# cfg.norm_rho_options asks for it, since printing it reads rho back every iteration
+def add_norm_rho_updater(hub_dict, cfg):
+    if _get(cfg, "use_norm_rho_updater", False):
+        hub_dict = extension_adder(hub_dict, NormRhoUpdater)
+        hub_dict["opt_kwargs"]["options"]["norm_rho_options"] = dict(_get(cfg, "norm_rho_options", {}))
+    return hub_dict
+
+
+# examples/farmer/farmer_cylinders.py:67-75 and 103-108 (cfg.use_norm_rho_converger,
+# cfg.primal_dual_converger, cfg.primal_dual_converger_tol; no tracker)
+def add_ph_converger(hub_dict, cfg):
+    conv = converger_from_cfg(cfg)
+    if conv is not None:
+        hub_dict["opt_kwargs"]["ph_converger"] = conv
+    if conv is PrimalDualConverger:
+        hub_dict["opt_kwargs"]["options"]["primal_dual_converger_options"] = {
+            "verbose": bool(_get(cfg, "verbose", False)),
+            "tol": _get(cfg, "primal_dual_converger_tol", 1e-2),
+        }
     return hub_dict
 
 

@@ -332,6 +332,45 @@ int phgpu_norm_rho_update(phgpu_handle h, const phgpu_norm_rho_params* prm, cons
                           const double* rho_last, const double* xbar_node, const double* xbar_prev,
                           double* rho, int64_t* counts, void* stream);
 
+/* Inner-bound candidates that are functions of all scenarios: x̄ itself
+ * (mpisppy/extensions/xhatxbar.py:38-55, cylinders/xhatxbar_bounder.py:96-104), the slam
+ * heuristics' column-wise max / min (cylinders/slam_heuristic.py:57-67 and 84) and the scenario
+ * closest to x̄ (extensions/xhatclosest.py:37-65).  Both entries are ordered on the stream and
+ * do not synchronise (the first use allocates their own workspace; phgpu_workspace_bytes grows
+ * only then); both work on a PHGPU_SHARED_MATRIX handle.  Inputs are finite: what a NaN in v
+ * gives is unspecified.
+ *
+ * phgpu_nonant_stats: v, device [nn*S], nonant values k-major and scenario-fastest (the layout
+ * of W and of a spoke's localnonants, not x[n*S]).  planes[4 * num_nodes * nlen_max], four
+ * node-indexed planes laid out like one half of node_buf ([g * nlen_max + off]), each over the
+ * local scenarios whose node at the nonant's depth is g:
+ *   plane 0   sum pcoef v        pcoef = prob_coeff, or pvar[k, s] with variable probabilities
+ *   plane 1   sum pcoef v^2      (the weights of phgpu_ph_reduce: xbars / xsqbars,
+ *                                phbase.py:54-79, which xhatxbar.py:49-51 fixes the nonants at
+ *                                and xhatclosest.py:40-42 measures against)
+ *   plane 2   max(-v) = -min v   slam_heuristic.py:65 with np.amin, negated
+ *   plane 3   max(v)             slam_heuristic.py:65 with np.amax
+ * An entry no local scenario reaches is 0 in planes 0-1 and -inf in planes 2-3, so the caller
+ * sums planes 0-1 over the ranks and takes ONE MAX all-reduce over planes 2-3 (the reference's
+ * Allreduce with mpi.MAX / mpi.MIN, slam_heuristic.py:84).  planes is overwritten in full.
+ * Planes 0-1 are deterministic wherever phgpu_ph_reduce is (wave-uniform nodes: per-wave
+ * partials, then an ordered final sum; a wave that spans nodes adds by fp64 atomics); planes
+ * 2-3 do not depend on the order. */
+int phgpu_nonant_stats(phgpu_handle h, const double* v, double* planes, void* stream);
+
+/* The local scenario closest to x̄ in truncated z-score (xhatclosest.py:37-51), two-stage
+ * handles only (depth 1, one node; -3 and nothing launched otherwise, as the reference's
+ * pre_iter0 refuses multistage, :91-93).  xbar_node, xsqbar_node: device [nlen_max] each, the
+ * reduced planes 0 and 1 of phgpu_nonant_stats or the two halves of node_buf.  For every
+ * local scenario s
+ *   dist[s] = sum_k [var_k > 0] min(3, |v[k, s] - x̄_k| / sqrt(var_k)),  var_k = x̄²_k - x̄_k x̄_k
+ * with k ascending and the test on var_k strict (:41-45).  dist: device [S] or NULL.
+ * best: device double[2], written last: the smallest dist and the LOWEST local index attaining
+ * it (the strict < scan of :46-51).  The ranks' agreement (MIN of the distance, then MAX of
+ * the rank among those attaining it, :53-65) is the caller's. */
+int phgpu_nonant_closest(phgpu_handle h, const double* v, const double* xbar_node,
+                         const double* xsqbar_node, double* dist, double* best, void* stream);
+
 /* Local probability-weighted sums (spopt.py:310-439) into out[5]:
  *   out[0] = sum_s prob_s * obj_s    out[1] = sum_s prob_s * bound_s
  *   out[2] = sum_s prob_s (E1)       out[3] = sum_{s feasible} prob_s, where feasible

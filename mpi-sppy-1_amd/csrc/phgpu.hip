@@ -230,6 +230,13 @@ struct phgpu_state {
     // path-6 epilogue)
     double* rs_part;
     int32_t* rs_node;
+    // phgpu_nonant_stats' per-wave partials and node tags (the same shapes) and
+    // phgpu_nonant_closest's per-block (distance, index) pairs [2 * blocks] and last-block
+    // counter, each allocated at the entry's first call
+    double* ns_part;
+    int32_t* ns_node;
+    double* nc_part;
+    int32_t* nc_cnt;
 };
 
 #define IX(k) ((size_t)(k) * (size_t)S + (size_t)s)
@@ -1275,7 +1282,26 @@ k_resid_partial(phgpu_state st, const double* __restrict__ x, const double* __re
 // nonant whose waves all share one node takes the fixed-order tree sum.
 // assign: the planes were not cleared (one tree node, every entry is some nonant's): the
 // fixed-order sum is stored, not added (as k_xbar_final's assign).
-__global__ void __launch_bounds__(XF_THREADS) k_resid_final(phgpu_state st, double* __restrict__ planes, int assign) {
+// MAXMASK: bit j set = plane j is a maximum, not a sum (phgpu_nonant_stats' planes 2 and 3;
+// cleared to -inf); part / node: the caller's per-wave partials and node tags.
+template <int MAXMASK>
+__device__ __forceinline__ double pl_id(int j) {
+    return ((MAXMASK >> j) & 1) ? -INFINITY : 0.0;
+}
+template <int MAXMASK>
+__device__ __forceinline__ double pl_op(int j, double a, double b) {
+    return ((MAXMASK >> j) & 1) ? fmax(a, b) : a + b;
+}
+template <int MAXMASK>
+__device__ __forceinline__ void pl_atomic(int j, double* p, double v) {
+    if ((MAXMASK >> j) & 1) atomicMax(p, v);
+    else atomicAdd(p, v);
+}
+
+template <int MAXMASK>
+__global__ void __launch_bounds__(XF_THREADS)
+k_resid_final(phgpu_state st, const double* __restrict__ part, const int32_t* __restrict__ node,
+              double* __restrict__ planes, int assign) {
     __shared__ int fnode[XF_THREADS], lnode[XF_THREADS];
     __shared__ double fv[RS_NV][XF_THREADS], lv[RS_NV][XF_THREADS];
     __shared__ int single;
@@ -1287,12 +1313,14 @@ __global__ void __launch_bounds__(XF_THREADS) k_resid_final(phgpu_state st, doub
     const int64_t C = (nw + XF_THREADS - 1) / XF_THREADS;
     const int64_t w0 = (int64_t)t * C, w1 = (w0 + C < nw) ? w0 + C : nw;
     int cur = -1, first = -1;
-    double a[RS_NV] = {0.0, 0.0, 0.0, 0.0}, a_first[RS_NV] = {0.0, 0.0, 0.0, 0.0};
+    double a[RS_NV], a_first[RS_NV];
+#pragma unroll
+    for (int j = 0; j < RS_NV; ++j) a[j] = a_first[j] = pl_id<MAXMASK>(j);
     for (int64_t w = w0; w < w1; ++w) {
-        const int gnode = st.rs_node[w * st.nn + k];
+        const int gnode = node[w * st.nn + k];
         double p[RS_NV];
 #pragma unroll
-        for (int j = 0; j < RS_NV; ++j) p[j] = st.rs_part[(w * st.nn + k) * RS_NV + j];
+        for (int j = 0; j < RS_NV; ++j) p[j] = part[(w * st.nn + k) * RS_NV + j];
         if (gnode < 0) continue;
         if (gnode != cur) {
             if (cur >= 0) {
@@ -1302,15 +1330,15 @@ __global__ void __launch_bounds__(XF_THREADS) k_resid_final(phgpu_state st, doub
                     for (int j = 0; j < RS_NV; ++j) a_first[j] = a[j];
                 } else {          // a complete middle run
 #pragma unroll
-                    for (int j = 0; j < RS_NV; ++j) atomicAdd(&planes[j * half + cur * st.nlen_max + off], a[j]);
+                    for (int j = 0; j < RS_NV; ++j) pl_atomic<MAXMASK>(j, &planes[j * half + cur * st.nlen_max + off], a[j]);
                 }
             }
             cur = gnode;
 #pragma unroll
-            for (int j = 0; j < RS_NV; ++j) a[j] = 0.0;
+            for (int j = 0; j < RS_NV; ++j) a[j] = pl_id<MAXMASK>(j);
         }
 #pragma unroll
-        for (int j = 0; j < RS_NV; ++j) a[j] += p[j];
+        for (int j = 0; j < RS_NV; ++j) a[j] = pl_op<MAXMASK>(j, a[j], p[j]);
     }
     if (t == 0) single = 1;
     if (first < 0) {  // zero or one run in this chunk: it is the first (and last) run
@@ -1319,7 +1347,7 @@ __global__ void __launch_bounds__(XF_THREADS) k_resid_final(phgpu_state st, doub
 #pragma unroll
         for (int j = 0; j < RS_NV; ++j) {
             fv[j][t] = a[j];
-            lv[j][t] = 0.0;
+            lv[j][t] = pl_id<MAXMASK>(j);
         }
     } else {
         fnode[t] = first;
@@ -1338,12 +1366,12 @@ __global__ void __launch_bounds__(XF_THREADS) k_resid_final(phgpu_state st, doub
     __syncthreads();
     if (single) {
 #pragma unroll
-        for (int j = 0; j < RS_NV; ++j) fv[j][t] += lv[j][t];
+        for (int j = 0; j < RS_NV; ++j) fv[j][t] = pl_op<MAXMASK>(j, fv[j][t], lv[j][t]);
         __syncthreads();
         for (int o = XF_THREADS / 2; o > 0; o >>= 1) {
             if (t < o) {
 #pragma unroll
-                for (int j = 0; j < RS_NV; ++j) fv[j][t] += fv[j][t + o];
+                for (int j = 0; j < RS_NV; ++j) fv[j][t] = pl_op<MAXMASK>(j, fv[j][t], fv[j][t + o]);
             }
             __syncthreads();
         }
@@ -1354,7 +1382,7 @@ __global__ void __launch_bounds__(XF_THREADS) k_resid_final(phgpu_state st, doub
 #pragma unroll
                 for (int j = 0; j < RS_NV; ++j) {
                     double* q = &planes[j * half + g0 * st.nlen_max + off];
-                    *q = assign ? fv[j][0] : *q + fv[j][0];
+                    *q = assign ? fv[j][0] : pl_op<MAXMASK>(j, *q, fv[j][0]);
                 }
             }
         }
@@ -1377,12 +1405,12 @@ __global__ void __launch_bounds__(XF_THREADS) k_resid_final(phgpu_state st, doub
                 if (fnode[u] < 0) continue;  // empty chunk
                 if (fnode[u] != g) break;
 #pragma unroll
-                for (int j = 0; j < RS_NV; ++j) sv[j] += fv[j][u];
+                for (int j = 0; j < RS_NV; ++j) sv[j] = pl_op<MAXMASK>(j, sv[j], fv[j][u]);
                 if (lnode[u] >= 0) break;    // the run ends inside chunk u
             }
         }
 #pragma unroll
-        for (int j = 0; j < RS_NV; ++j) atomicAdd(&planes[j * half + g * st.nlen_max + off], sv[j]);
+        for (int j = 0; j < RS_NV; ++j) pl_atomic<MAXMASK>(j, &planes[j * half + g * st.nlen_max + off], sv[j]);
     }
 }
 
@@ -1449,6 +1477,171 @@ k_norm_rho_update(phgpu_state st, phgpu_norm_rho_params prm, const double* __res
             for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, WAVE);
             if ((threadIdx.x & (WAVE - 1)) == 0 && v) atomicAdd(&counts[a], (unsigned long long)v);
         }
+    }
+}
+
+// ------------------------------------------------------------------ xhat candidates
+// Per-node statistics of a nonant array v[nn*S] (k-major, like W or a spoke's localnonants):
+// the candidates of XhatXbar (extensions/xhatxbar.py:38-55: the node's x̄), the slam
+// heuristics (cylinders/slam_heuristic.py:57-67, 84: the column-wise max / min) and the x̄ /
+// x̄² XhatClosest measures against (extensions/xhatclosest.py:37-45), by the scheme of
+// k_resid_partial / k_resid_final: planes 0-1 are sums, planes 2-3 maxima (the minimum is
+// stored negated, so that one MAX over the ranks serves both).
+#define NS_KU 4  // nonants per grid row: their loads are in flight together
+
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, WAVE));
+    return v;
+}
+
+// planes 0-1 to 0, planes 2-3 to -inf (what an entry no local scenario reaches keeps)
+__global__ void __launch_bounds__(256) k_nstats_clear(double* __restrict__ planes, int64_t half) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < RS_NV * half; i += stride)
+        planes[i] = i < 2 * half ? 0.0 : -INFINITY;
+}
+
+// One lane per scenario, NS_KU nonants per grid row.  A wave whose scenarios share one node
+// writes one partial per plane (deterministic); a mixed wave goes to the planes per lane by
+// fp64 atomics (add / max).
+__global__ void __launch_bounds__(BLOCK)
+k_nstats_partial(phgpu_state st, const double* __restrict__ v, double* __restrict__ planes) {
+    const int64_t S = st.S;
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t wave = s / WAVE;
+    const bool act = s < S;
+    const int64_t half = (int64_t)st.num_nodes * st.nlen_max;
+    const int k0 = blockIdx.y * NS_KU;
+    double val[NS_KU], pc[NS_KU];
+    int gn[NS_KU];
+#pragma unroll
+    for (int u = 0; u < NS_KU; ++u) {
+        const int k = k0 + u;
+        const bool on = act && k < st.nn;
+        const int d = k < st.nn ? st.nonant_depth[k] : 0;
+        gn[u] = on ? st.node_of[IX(d)] : -1;
+        val[u] = on ? v[IX(k)] : 0.0;
+        pc[u] = on ? (st.pvar ? st.pvar[IX(k)] : st.pcoef[IX(d)]) : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < NS_KU; ++u) {
+        const int k = k0 + u;
+        if (k >= st.nn) break;
+        const int gnode = gn[u];
+        double w[RS_NV] = {pc[u] * val[u], pc[u] * val[u] * val[u], act ? -val[u] : -INFINITY,
+                           act ? val[u] : -INFINITY};
+        const int g0 = __shfl(gnode, 0, WAVE);
+        const bool uniform = !__any(act && gnode != g0);
+        if (uniform) {
+            w[0] = wave_sum(w[0]);
+            w[1] = wave_sum(w[1]);
+            w[2] = wave_max(w[2]);
+            w[3] = wave_max(w[3]);
+            if ((threadIdx.x & (WAVE - 1)) == 0) {
+#pragma unroll
+                for (int j = 0; j < RS_NV; ++j) st.ns_part[(wave * st.nn + k) * RS_NV + j] = w[j];
+                st.ns_node[wave * st.nn + k] = g0;
+            }
+        } else {
+            if (act) {
+                const int64_t o = (int64_t)gnode * st.nlen_max + st.nonant_off[k];
+                atomicAdd(&planes[o], w[0]);
+                atomicAdd(&planes[half + o], w[1]);
+                atomicMax(&planes[2 * half + o], w[2]);
+                atomicMax(&planes[3 * half + o], w[3]);
+            }
+            if ((threadIdx.x & (WAVE - 1)) == 0) st.ns_node[wave * st.nn + k] = -1;
+        }
+    }
+}
+
+// xhatclosest.py:37-51 for a two-stage handle: one lane per scenario sums, k ascending, the
+// truncated z-scores min(3, |v - x̄| / sqrt(var)) of the nonants with var = x̄² - x̄ x̄ > 0
+// (strict), NC_KU loads of v in flight.  The smallest distance and the lowest local index
+// attaining it (the reference's strict < scan): (distance, index) pairs reduced per wave and
+// per block, the block's pair swapped into bpart, and the block with the last ticket reduces
+// the pairs and stores best (conv_last_block's exchange / ticket chain: agent-scope atomic
+// read-modify-writes, no fence).  The lexicographic minimum does not depend on the order.
+// The index travels as a double (exact below 2^53), as best[1] returns it.
+#define NC_T 256
+#define NC_KU 4
+__device__ __forceinline__ void argmin_take(double& d, double& i, double od, double oi) {
+    if (od < d || (od == d && oi < i)) {
+        d = od;
+        i = oi;
+    }
+}
+
+__global__ void __launch_bounds__(NC_T)
+k_nonant_closest(phgpu_state st, const double* __restrict__ v, const double* __restrict__ xbar_node,
+                 const double* __restrict__ xsqbar_node, double* __restrict__ dist, double* __restrict__ bpart,
+                 int32_t* __restrict__ cnt, double* __restrict__ best) {
+    __shared__ double rd[NC_T / WAVE], ri[NC_T / WAVE];
+    __shared__ int last;
+    const int64_t S = st.S;
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool act = s < S;
+    const int nn = st.nn;
+    double acc = 0.0;
+    for (int k0 = 0; k0 < nn; k0 += NC_KU) {
+        double val[NC_KU];
+#pragma unroll
+        for (int u = 0; u < NC_KU; ++u) val[u] = (act && k0 + u < nn) ? v[IX(k0 + u)] : 0.0;
+#pragma unroll
+        for (int u = 0; u < NC_KU; ++u) {
+            if (k0 + u >= nn) break;
+            const int o = st.nonant_off[k0 + u];
+            const double xb = xbar_node[o];
+            const double var = xsqbar_node[o] - xb * xb;
+            if (var > 0.0) acc += fmin(3.0, fabs(val[u] - xb) / sqrt(var));
+        }
+    }
+    if (act && dist) dist[s] = acc;
+    double d = act ? acc : INFINITY, i = act ? (double)s : INFINITY;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        argmin_take(d, i, __shfl_down(d, off, WAVE), __shfl_down(i, off, WAVE));
+    const int wv = threadIdx.x / WAVE;
+    if ((threadIdx.x & (WAVE - 1)) == 0) {
+        rd[wv] = d;
+        ri[wv] = i;
+    }
+    __syncthreads();
+    const int nblk = (int)gridDim.x;
+    if (threadIdx.x == 0) {
+        for (int u = 1; u < NC_T / WAVE; ++u) argmin_take(d, i, rd[u], ri[u]);
+        const double o0 = __hip_atomic_exchange(&bpart[2 * blockIdx.x], d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const double o1 =
+            __hip_atomic_exchange(&bpart[2 * blockIdx.x + 1], i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // both swaps have returned before the ticket is taken (see conv_last_block)
+        asm volatile("" ::"v"(o0), "v"(o1) : "memory");
+        const int tk = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last = tk == nblk - 1;
+    }
+    __syncthreads();
+    if (!last) return;
+    d = INFINITY;
+    i = INFINITY;
+    for (int b = threadIdx.x; b < nblk; b += blockDim.x) {
+        const double od = __hip_atomic_fetch_add(&bpart[2 * b], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const double oi = __hip_atomic_fetch_add(&bpart[2 * b + 1], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        argmin_take(d, i, od, oi);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        argmin_take(d, i, __shfl_down(d, off, WAVE), __shfl_down(i, off, WAVE));
+    __syncthreads();
+    if ((threadIdx.x & (WAVE - 1)) == 0) {
+        rd[wv] = d;
+        ri[wv] = i;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int u = 1; u < NC_T / WAVE; ++u) argmin_take(d, i, rd[u], ri[u]);
+        best[1] = i;
+        best[0] = d;
+        __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -3641,7 +3834,8 @@ extern "C" int phgpu_ph_residuals(phgpu_handle h, const double* x, const double*
     g.y = (unsigned)h->nn;
     hipLaunchKernelGGL(k_resid_partial, g, dim3(BLOCK), 0, st, *h, x, xbar, rho, planes, rho_last);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_resid_final, dim3(h->nn), dim3(XF_THREADS), 0, st, *h, planes, assign);
+    hipLaunchKernelGGL(k_resid_final<0>, dim3(h->nn), dim3(XF_THREADS), 0, st, *h, (const double*)h->rs_part,
+                       (const int32_t*)h->rs_node, planes, assign);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -3658,6 +3852,67 @@ extern "C" int phgpu_norm_rho_update(phgpu_handle h, const phgpu_norm_rho_params
     const int64_t bx = std::min<int64_t>((h->S + NR_T - 1) / NR_T, std::max<int64_t>(1, UPD_BLOCKS / h->nn));
     hipLaunchKernelGGL(k_norm_rho_update, dim3((unsigned)bx, (unsigned)h->nn), dim3(NR_T), 0, st, *h, *prm, planes,
                        rho_last, xbar_node, xbar_prev, rho, (unsigned long long*)counts);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// extensions/xhatxbar.py:38-55, cylinders/slam_heuristic.py:57-84 (include/phgpu.h)
+extern "C" int phgpu_nonant_stats(phgpu_handle h, const double* v, double* planes, void* stream) {
+    if (!h || !v || !planes) return set_err(-1, "null argument");
+    FLUSH_STEP(h);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t half = (int64_t)h->num_nodes * h->nlen_max;
+    // one tree node whose every entry is a nonant's: every wave is uniform and the final
+    // kernel stores all four planes in full (as phgpu_ph_residuals' assign)
+    const int assign = (h->num_nodes == 1 && h->nlen_max == h->nn) ? 1 : 0;
+    if (!assign) {
+        hipLaunchKernelGGL(k_nstats_clear, dim3((unsigned)std::min<int64_t>((RS_NV * half + 255) / 256, 256)),
+                           dim3(256), 0, st, planes, half);
+        HIPCHK(hipGetLastError());
+    }
+    if (h->nn == 0) return 0;
+    if (!h->ns_part) {  // first use: workspace of its own
+        const size_t cnt = (size_t)h->nwaves * (size_t)h->nn;
+        int rc = dalloc(h, &h->ns_part, cnt * RS_NV);
+        if (!rc) rc = dalloc(h, &h->ns_node, cnt);
+        if (rc) {
+            if (h->ns_part) (void)hipFree(h->ns_part);
+            h->ns_part = nullptr;
+            return rc;
+        }
+    }
+    dim3 g = grid_for(h->S);
+    g.y = (unsigned)((h->nn + NS_KU - 1) / NS_KU);
+    hipLaunchKernelGGL(k_nstats_partial, g, dim3(BLOCK), 0, st, *h, v, planes);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_resid_final<0xC>, dim3(h->nn), dim3(XF_THREADS), 0, st, *h, (const double*)h->ns_part,
+                       (const int32_t*)h->ns_node, planes, assign);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// extensions/xhatclosest.py:37-51
+extern "C" int phgpu_nonant_closest(phgpu_handle h, const double* v, const double* xbar_node,
+                                    const double* xsqbar_node, double* dist, double* best, void* stream) {
+    if (!h || !v || !xbar_node || !xsqbar_node || !best) return set_err(-1, "null argument");
+    if (h->depth != 1 || h->num_nodes != 1)
+        return set_err(-3, "phgpu_nonant_closest: two-stage handles only (depth %d, %d nodes)", h->depth,
+                       h->num_nodes);
+    FLUSH_STEP(h);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t nblk = (h->S + NC_T - 1) / NC_T;
+    if (!h->nc_part) {  // first use: the block pairs and the (zeroed) last-block counter
+        int rc = dalloc(h, &h->nc_part, (size_t)(2 * nblk));
+        if (!rc) rc = dalloc(h, &h->nc_cnt, 1);
+        if (rc) {
+            if (h->nc_part) (void)hipFree(h->nc_part);
+            h->nc_part = nullptr;
+            return rc;
+        }
+        HIPCHK(hipMemsetAsync(h->nc_cnt, 0, sizeof(int32_t), st));
+    }
+    hipLaunchKernelGGL(k_nonant_closest, dim3((unsigned)nblk), dim3(NC_T), 0, st, *h, v, xbar_node, xsqbar_node, dist,
+                       h->nc_part, h->nc_cnt, best);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -3744,7 +3999,8 @@ extern "C" int phgpu_destroy(phgpu_handle h) {
     if (h->stats_gen) (void)hipFree(h->stats_gen);
     {
         void* more[] = {h->xp[0], h->xp[1], h->xp_node[0], h->xp_node[1], h->xp_dirty[0], h->xp_dirty[1],
-                        h->cpart_blk, h->blk_cnt, h->nb_idx, h->rs_part, h->rs_node};
+                        h->cpart_blk, h->blk_cnt, h->nb_idx, h->rs_part, h->rs_node,
+                        h->ns_part, h->ns_node, h->nc_part, h->nc_cnt};
         for (void* p : more)
             if (p) (void)hipFree(p);
     }

@@ -64,7 +64,8 @@ EXPORTS = ["phgpu_default_options", "phgpu_create", "phgpu_create2", "phgpu_set_
            "phgpu_ph_update_ex", "phgpu_ph_step_local", "phgpu_ph_step_defer", "phgpu_ph_step_flush",
            "phgpu_set_nonant_probs", "phgpu_set_ipm_tuning", "phgpu_ipm_prof",
            "phgpu_ph_loop", "phgpu_stream_info", "phgpu_comm_unique_id", "phgpu_comm_init",
-           "phgpu_allreduce_sum", "phgpu_ph_residuals", "phgpu_norm_rho_update"]
+           "phgpu_allreduce_sum", "phgpu_ph_residuals", "phgpu_norm_rho_update",
+           "phgpu_nonant_stats", "phgpu_nonant_closest"]
 
 _lib = None
 
@@ -116,6 +117,8 @@ def load(path=None):
     lib.phgpu_ph_residuals.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     lib.phgpu_norm_rho_update.argtypes = [c_vp, ctypes.POINTER(NormRhoParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                           c_vp]
+    lib.phgpu_nonant_stats.argtypes = [c_vp, c_vp, c_vp, c_vp]
+    lib.phgpu_nonant_closest.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     lib.phgpu_ipm_info.argtypes = [c_vp, ctypes.POINTER(c_dbl)]
     lib.phgpu_ipm_prof.argtypes = [c_vp, ctypes.POINTER(ctypes.c_ulonglong), c_i64]
     lib.phgpu_ipm_prof.restype = c_i64

@@ -9,6 +9,9 @@ GPU, scenario-fastest ``[k, S]``) and sequences the per-PH-iteration work:
     Ebound/Eobj/E1  -> phgpu_expectations + all-reduce (spopt.py:310-439)
     adaptive rho    -> phgpu_ph_residuals + all-reduce + phgpu_norm_rho_update
                                                        (extensions/norm_rho_updater.py:55-143)
+    xhat candidates -> phgpu_nonant_stats + SUM / MAX all-reduces, phgpu_nonant_closest
+                                                       (extensions/xhatxbar.py, xhatclosest.py,
+                                                        cylinders/slam_heuristic.py)
 
 All launches go to torch's current stream; host synchronisation happens only where
 the reference needs a host scalar (the convergence test, bounds).
@@ -127,7 +130,8 @@ class PHEngine:
         self.calls = {"ph_reduce": 0, "ph_update_ex": 0, "ph_step_local": 0, "ph_step_defer": 0,
                       "allreduce_xbar": 0, "allreduce_conv_side": 0, "allreduce_conv_main": 0, "xbar_ahead_used": 0,
                       "ph_loop": 0, "ph_residuals": 0, "norm_rho_update": 0, "allreduce_resid": 0,
-                      "solve_deferred": 0}
+                      "solve_deferred": 0, "nonant_stats": 0, "nonant_closest": 0, "allreduce_stats_sum": 0,
+                      "allreduce_stats_max": 0}
         # several ranks: the conv all-reduce on a side stream under the next solve (False: on
         # the launch stream ahead of it -- bench.py --no-conv-overlap, the comparison case)
         self.overlap_conv = True
@@ -752,6 +756,66 @@ class PHEngine:
     def rho_norm(self):
         """NormRhoConverger._compute_rho_norm (norm_rho_converger.py:23-29)."""
         return float(self.residual_planes()[3].sum())
+
+    # -------------------------------------------------------------- xhat candidates
+    def _nonant_arg(self, v):
+        v = v.to(device=self.device, dtype=torch.float64).contiguous()
+        assert tuple(v.shape) == (max(self.nn, 1), self.S), v.shape
+        return v
+
+    def nonant_stats(self, v):
+        """Per-node statistics of a nonant array ``v`` (device [nn, S], the layout of W and of a
+        spoke's localnonants; phgpu_nonant_stats): a device [4, num_nodes, nlen_max] tensor
+        of the pcoef-weighted sums of v and v² (x̄ and x̄², phbase.py:54-87), -min v and max v
+        (slam_heuristic.py:57-84), reduced over the ranks by one SUM (planes 0-1) and one MAX
+        (planes 2-3) all-reduce.  Entries no scenario of any rank reaches: 0 / -inf."""
+        self._flush_step()
+        half = self.num_nodes * self.nlen_max
+        if getattr(self, "nstats", None) is None:
+            self.nstats = torch.empty(4 * half, dtype=torch.float64, device=self.device)
+        v = self._nonant_arg(v)
+        self.calls["nonant_stats"] += 1
+        _lib.check(self.lib.phgpu_nonant_stats(self.h, _ptr(v), _ptr(self.nstats), self._stream()),
+                   "phgpu_nonant_stats")
+        if self.comm.size > 1:
+            self.calls["allreduce_stats_sum"] += 1
+            self._ar(self.nstats[:2 * half])
+            self.calls["allreduce_stats_max"] += 1
+            self.comm.allreduce_max_(self.nstats[2 * half:])
+        return self.nstats.view(4, self.num_nodes, self.nlen_max)
+
+    def closest_scenario(self, v, xbar_node, xsqbar_node):
+        """The scenario of ``v`` (device [nn, S]) closest to x̄ in truncated z-score
+        (phgpu_nonant_closest, xhatclosest.py:37-65; two-stage only): (smallest distance,
+        rank, local index), the same on every rank.  ``xbar_node`` / ``xsqbar_node``: device
+        [nlen_max] tensors, the reduced planes 0 / 1 of ``nonant_stats`` or the halves of
+        node_buf.  Ties within a rank go to the lowest index, between ranks to the highest
+        rank (a MAX of -distance, then a MAX of rank-or--1, as the reference's two
+        Allreduces).  ``closest_dist`` keeps the local distances (device [S])."""
+        self._flush_step()
+        if getattr(self, "closest_dist", None) is None:
+            self.closest_dist = torch.empty(self.S, dtype=torch.float64, device=self.device)
+            self._closest_best = torch.empty(2, dtype=torch.float64, device=self.device)
+        v = self._nonant_arg(v)
+        xb = xbar_node.to(device=self.device, dtype=torch.float64).contiguous()
+        xs = xsqbar_node.to(device=self.device, dtype=torch.float64).contiguous()
+        assert xb.numel() >= self.nlen_max and xs.numel() >= self.nlen_max, (xb.shape, xs.shape)
+        self.calls["nonant_closest"] += 1
+        _lib.check(self.lib.phgpu_nonant_closest(self.h, _ptr(v), _ptr(xb), _ptr(xs), _ptr(self.closest_dist),
+                                                 _ptr(self._closest_best), self._stream()), "phgpu_nonant_closest")
+        if self.comm.size == 1:
+            d, i = self._closest_best.cpu().tolist()
+            return d, 0, int(i)
+        t = -self._closest_best[:1].clone()
+        self.comm.allreduce_max_(t)
+        d, i = self._closest_best.cpu().tolist()
+        gmin = -float(t.item())
+        r = torch.tensor([float(self.comm.rank) if d <= gmin else -1.0], dtype=torch.float64, device=self.device)
+        self.comm.allreduce_max_(r)
+        win = int(r.item())
+        li = torch.tensor([float(i) if win == self.comm.rank else -1.0], dtype=torch.float64, device=self.device)
+        self.comm.allreduce_max_(li)
+        return gmin, win, int(li.item())
 
     def convergence_diff(self):
         """phbase.py:330-343: sum over ranks of per-rank means, / n_proc (host float)."""

@@ -90,6 +90,7 @@ class SPOpt(SPBase):
             self.extobject = extensions(self) if extension_kwargs is None else extensions(self, **extension_kwargs)
         self.spcomm = None
         self.engine = None
+        self._fixed = False
         self.solve_times = []
         self.pdhg_iters = []
 
@@ -217,6 +218,33 @@ class SPOpt(SPBase):
     def infeas_prob(self):
         e = self.engine.expectations()
         return e[2] - e[3]
+
+    # -- fixing the nonants (Xhat_Eval, XhatBase._try_one, and the xhat extensions of a PH object)
+    def _node_table(self, cache):
+        """dict node name -> values (spopt.py:557-592 cache) -> device [num_nodes, nlen_max]."""
+        import torch
+        e = self.engine
+        tab = np.zeros((e.num_nodes, e.nlen_max))
+        for g, nd in enumerate(e.node_names):
+            if nd in cache and cache[nd] is not None:
+                v = np.asarray(cache[nd], dtype=np.float64).reshape(-1)
+                tab[g, :len(v)] = v
+        return torch.from_numpy(tab).to(e.device)
+
+    # spopt.py:557-592
+    def _fix_nonants(self, cache):
+        """Fix the nonants of all local scenarios: ``cache`` is {node name: values} or a
+        device [num_nodes, nlen_max] tensor (global node order)."""
+        import torch
+        tab = cache if torch.is_tensor(cache) else self._node_table(cache)
+        self.engine.fix_nonants_by_node(tab)
+        self._fixed = True
+
+    # spopt.py:638-660
+    def _restore_nonants(self):
+        if self.engine is not None and self._fixed:
+            self.engine.fix_nonants(None)
+        self._fixed = False
 
     # -- values back into the LinearModels (for denouement / writers)
     def load_solutions_to_models(self):

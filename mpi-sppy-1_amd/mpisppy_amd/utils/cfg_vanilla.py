@@ -1,6 +1,7 @@
 """Cylinder dict builders (mirrors mpisppy/utils/cfg_vanilla.py:41-495 for the cylinders
-this engine serves: ph_hub, lagrangian_spoke, xhatshuffle_spoke; extension_adder and
-add_wxbar_read_write for the hub's extensions).
+this engine serves: ph_hub, lagrangian_spoke, xhatshuffle_spoke, xhatxbar_spoke,
+slammax_spoke, slammin_spoke; extension_adder and add_wxbar_read_write for the hub's
+extensions).
 
 ``cfg`` is any object with the reference's config attribute names (solver_name,
 default_rho, max_iterations, rel_gap, ...); missing attributes take the reference's
@@ -10,6 +11,8 @@ import copy
 
 from ..cylinders.hub import PHHub
 from ..cylinders.lagrangian_bounder import LagrangianOuterBound
+from ..cylinders.slam_heuristic import SlamMaxHeuristic, SlamMinHeuristic
+from ..cylinders.xhatxbar_bounder import XhatXbarInnerBound
 from ..cylinders.xhatshufflelooper_bounder import XhatShuffleInnerBound
 from ..convergers.norm_rho_converger import NormRhoConverger
 from ..convergers.primal_dual_converger import PrimalDualConverger
@@ -124,6 +127,62 @@ def xhatshuffle_spoke(cfg, scenario_creator, scenario_denouement, all_scenario_n
             "all_nodenames": all_nodenames,
         },
     }
+
+
+# cfg_vanilla.py:424-454
+def xhatxbar_spoke(cfg, scenario_creator, scenario_denouement, all_scenario_names, scenario_creator_kwargs=None,
+                   variable_probability=None, all_nodenames=None):
+    shoptions = shared_options(cfg)
+    xhat_options = copy.deepcopy(shoptions)
+    xhat_options["bundles_per_rank"] = 0
+    xhat_options["xhat_xbar_options"] = {
+        "xhat_solver_options": shoptions["iterk_solver_options"],
+        "scen_limit": _get(cfg, "xhat_scen_limit", 3),
+        "dump_prefix": "delme",
+        "csvname": "xbar.csv",
+    }
+    return {
+        "spoke_class": XhatXbarInnerBound,
+        "opt_class": Xhat_Eval,
+        "opt_kwargs": {
+            "options": xhat_options,
+            "all_scenario_names": all_scenario_names,
+            "scenario_creator": scenario_creator,
+            "scenario_creator_kwargs": scenario_creator_kwargs,
+            "scenario_denouement": scenario_denouement,
+            "variable_probability": variable_probability,
+            "all_nodenames": all_nodenames,
+        },
+    }
+
+
+def _slam_spoke(spoke_class, cfg, scenario_creator, scenario_denouement, all_scenario_names,
+                scenario_creator_kwargs):
+    xhat_options = copy.deepcopy(shared_options(cfg))
+    xhat_options["bundles_per_rank"] = 0
+    return {
+        "spoke_class": spoke_class,
+        "opt_class": Xhat_Eval,
+        "opt_kwargs": {
+            "options": xhat_options,
+            "all_scenario_names": all_scenario_names,
+            "scenario_creator": scenario_creator,
+            "scenario_creator_kwargs": scenario_creator_kwargs,
+            "scenario_denouement": scenario_denouement,
+        },
+    }
+
+
+# cfg_vanilla.py:554-576
+def slammax_spoke(cfg, scenario_creator, scenario_denouement, all_scenario_names, scenario_creator_kwargs=None):
+    return _slam_spoke(SlamMaxHeuristic, cfg, scenario_creator, scenario_denouement, all_scenario_names,
+                       scenario_creator_kwargs)
+
+
+# cfg_vanilla.py:578-600
+def slammin_spoke(cfg, scenario_creator, scenario_denouement, all_scenario_names, scenario_creator_kwargs=None):
+    return _slam_spoke(SlamMinHeuristic, cfg, scenario_creator, scenario_denouement, all_scenario_names,
+                       scenario_creator_kwargs)
 
 
 # cfg_vanilla.py:164-181

@@ -28,7 +28,6 @@ class Xhat_Eval(SPOpt):
                          mpicomm=mpicomm, scenario_creator_kwargs=scenario_creator_kwargs,
                          variable_probability=variable_probability)
         self.verbose = options.get("verbose", False)
-        self._fixed = False
 
     # xhat_eval.py:113-139
     def _lazy_create_solvers(self):
@@ -36,30 +35,10 @@ class Xhat_Eval(SPOpt):
             self._create_solvers()
             self.engine.set_terms(0, 0)
 
-    def _node_table(self, cache):
-        """dict node name -> values (spopt.py:557-592 cache) -> device [num_nodes, nlen_max]."""
-        e = self.engine
-        tab = np.zeros((e.num_nodes, e.nlen_max))
-        for g, nd in enumerate(e.node_names):
-            if nd in cache and cache[nd] is not None:
-                v = np.asarray(cache[nd], dtype=np.float64).reshape(-1)
-                tab[g, :len(v)] = v
-        return torch.from_numpy(tab).to(e.device)
-
-    # spopt.py:557-592
+    # spopt.py:557-592 (SPOpt._fix_nonants, once the solvers exist)
     def _fix_nonants(self, cache):
-        """Fix the nonants of all local scenarios: ``cache`` is {node name: values} or a
-        device [num_nodes, nlen_max] tensor (global node order)."""
         self._lazy_create_solvers()
-        tab = cache if torch.is_tensor(cache) else self._node_table(cache)
-        self.engine.fix_nonants_by_node(tab)
-        self._fixed = True
-
-    # spopt.py:638-660
-    def _restore_nonants(self):
-        if self.engine is not None and self._fixed:
-            self.engine.fix_nonants(None)
-        self._fixed = False
+        super()._fix_nonants(cache)
 
     # xhat_eval.py:141-209
     def solve_loop(self, solver_options=None, use_scenarios_not_subproblems=False, dtiming=False,

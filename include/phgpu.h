@@ -371,6 +371,62 @@ int phgpu_nonant_stats(phgpu_handle h, const double* v, double* planes, void* st
 int phgpu_nonant_closest(phgpu_handle h, const double* v, const double* xbar_node,
                          const double* xsqbar_node, double* dist, double* best, void* stream);
 
+/* Cost-proportional rho, rho_k ~ |cost_k| / |x_k - x̄_k|, set when the dual metric stalls:
+ * mpisppy/utils/gradient.py (Find_Grad), utils/find_rho.py (Find_Rho), utils/wtracker.py
+ * (WTracker.W_diff) and extensions/gradient_extension.py.  All four entries are ordered on the
+ * stream and do not synchronise (the first use allocates their own workspace;
+ * phgpu_workspace_bytes grows only then), work on a PHGPU_SHARED_MATRIX handle, and give the
+ * same bits on every run.
+ *
+ * phgpu_grad_cost: cost[k, s] = -(c[col_k, s] + q[col_k, s] xn[k, s]) in original (unscaled)
+ * units, the negated derivative of the stored objective c.x + 1/2 x.diag(q).x at the nonant
+ * values xn: Find_Grad.compute_grad, gradient.py:65-81.  The reference fixes the nonants at
+ * xhat, solves, unfixes and restores (:95-122) only to move pynumero's evaluation point; q is
+ * diagonal here, so the nonants' derivative depends on xn alone and no solve is needed.
+ * (compute_grad indexes the gradient, which is in NLP variable order, by nonant position, :78-80;
+ * this entry gives the derivative with respect to the nonant itself.)
+ *   xn, cost: device [nn*S], k-major and scenario-fastest (the layout of W). */
+int phgpu_grad_cost(phgpu_handle h, const double* xn, double* cost, void* stream);
+
+/* WTracker.W_diff, wtracker.py:141-154: out[0] = sum_{k,s} |W[k,s] - W_prev[k,s]| / (S nn) over
+ * the local scenarios, and W_prev = W in the same pass.  The ranks' combination is the
+ * caller's: the reference sums the ranks' means and divides by n_proc (:155-157, as for
+ * conv_local); the engine weights every rank's mean by its share of the scenarios, which is the
+ * same number for an even split and does not depend on the split otherwise.
+ *   W: device [nn*S], read; W_prev: device [nn*S], rewritten; out: device double[1]. */
+int phgpu_w_diff(phgpu_handle h, const double* W, double* W_prev, double* out, void* stream);
+
+/* The ratios of Find_Rho.compute_rho (find_rho.py:170-203) reduced per nonant; two-stage
+ * handles only (depth 1, one node; -3 and nothing launched otherwise: the reference asserts
+ * node.name == "ROOT", :89, :109, :128).  r[k, s] = |cost[k, s]| / denominator, with
+ *   gden == NULL   the scenario's own denominator d_s = max over its nonants j of
+ *                  max(|x_j - x̄_j|, 2 (x_j - x̄_j)^2): np.max((w_denom, prox_denom)) at :189 is
+ *                  one scalar per scenario (_w_denom :78-95, _prox_denom :98-115)
+ *   gden given     gden[off_k], device [nlen_max]: _grad_denom (:118-147), i.e.
+ *                  max(1 / rho_relative_bound, the ranks' sum of plane 1 of phgpu_ph_residuals)
+ * planes[3 * num_nodes * nlen_max], laid out like phgpu_nonant_stats' planes:
+ *   plane 0   sum_s r (unweighted)     plane 1   max(-r) = -min r     plane 2   max(r)
+ * over the local scenarios; an entry without a nonant is 0 / -inf / -inf.  The caller takes one
+ * SUM (plane 0) and one MAX (planes 1-2) all-reduce over the ranks.  Division is IEEE, as
+ * numpy's: a zero denominator gives +inf; what 0 / 0 gives is unspecified.  Plane 0: per-wave
+ * partials and an ordered final sum, as phgpu_ph_reduce.
+ *   cost: device [nn*S]; x[n*S], xbar[nn*S]: device, read when gden is NULL. */
+int phgpu_rho_ratio_stats(phgpu_handle h, const double* cost, const double* x, const double* xbar,
+                          const double* gden, double* planes, void* stream);
+
+/* Find_Rho._order_stat (find_rho.py:150-168) of every nonant's ratios, after the ranks'
+ * reductions of planes, written to rho[k, s] of every local scenario (the rho_setter loop of
+ * gradient_extension.py:85-94); two-stage handles only (-3).  With mean = plane 0 / S_total
+ * (S_total: scenarios of all ranks), min = -plane 1, max = plane 2 and a = order_stat in [0, 1]:
+ *   a == 0.5: mean;   a < 0.5: min + 2 a (mean - min);   a > 0.5: (2 mean - max) + 2 a (max - mean)
+ * gate: device double[2] = {previous, current} dual metric (the ranks' W_diff), or NULL.  rho is
+ * written only if |(previous - current) / previous| <= thr, which NaN and inf fail
+ * (_update_rho_dual_based, gradient_extension.py:65-68, where thr is 0.05); NULL always writes.
+ * With the gate closed no byte of rho is stored.  applied: device int32[1] or NULL, 1 if rho
+ * was written, else 0. */
+int phgpu_rho_from_stats(phgpu_handle h, const double* planes, int64_t S_total, double order_stat,
+                         const double* gate, double thr, double* rho, int32_t* applied, void* stream);
+
 /* Local probability-weighted sums (spopt.py:310-439) into out[5]:
  *   out[0] = sum_s prob_s * obj_s    out[1] = sum_s prob_s * bound_s
  *   out[2] = sum_s prob_s (E1)       out[3] = sum_{s feasible} prob_s, where feasible

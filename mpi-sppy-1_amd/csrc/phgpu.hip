@@ -17,6 +17,10 @@
 //   NormRhoUpdater residuals and rule   extensions/norm_rho_updater.py:55-143
 //   converger sums                      convergers/primal_dual_converger.py:58-110,
 //                                       convergers/norm_rho_converger.py:23-29
+//   gradient cost, W_diff, cost-proportional rho
+//                                       utils/gradient.py:65-81, utils/wtracker.py:134-157,
+//                                       utils/find_rho.py:78-203,
+//                                       extensions/gradient_extension.py:65-95
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -237,6 +241,13 @@ struct phgpu_state {
     int32_t* ns_node;
     double* nc_part;
     int32_t* nc_cnt;
+    // phgpu_w_diff's per-block partials [WD_BLOCKS] and last-block counter, and
+    // phgpu_rho_ratio_stats' per-wave partials [nwaves * nn * 3] and node tags [nwaves * nn],
+    // each allocated at the entry's first call
+    double* wd_part;
+    int32_t* wd_cnt;
+    double* rr_part;
+    int32_t* rr_node;
 };
 
 #define IX(k) ((size_t)(k) * (size_t)S + (size_t)s)
@@ -1283,7 +1294,8 @@ k_resid_partial(phgpu_state st, const double* __restrict__ x, const double* __re
 // assign: the planes were not cleared (one tree node, every entry is some nonant's): the
 // fixed-order sum is stored, not added (as k_xbar_final's assign).
 // MAXMASK: bit j set = plane j is a maximum, not a sum (phgpu_nonant_stats' planes 2 and 3;
-// cleared to -inf); part / node: the caller's per-wave partials and node tags.
+// cleared to -inf); part / node: the caller's per-wave partials and node tags; NV: the number
+// of planes (and of values per (wave, nonant) in part), RS_NV unless stated.
 template <int MAXMASK>
 __device__ __forceinline__ double pl_id(int j) {
     return ((MAXMASK >> j) & 1) ? -INFINITY : 0.0;
@@ -1298,12 +1310,12 @@ __device__ __forceinline__ void pl_atomic(int j, double* p, double v) {
     else atomicAdd(p, v);
 }
 
-template <int MAXMASK>
+template <int MAXMASK, int NV = RS_NV>
 __global__ void __launch_bounds__(XF_THREADS)
 k_resid_final(phgpu_state st, const double* __restrict__ part, const int32_t* __restrict__ node,
               double* __restrict__ planes, int assign) {
     __shared__ int fnode[XF_THREADS], lnode[XF_THREADS];
-    __shared__ double fv[RS_NV][XF_THREADS], lv[RS_NV][XF_THREADS];
+    __shared__ double fv[NV][XF_THREADS], lv[NV][XF_THREADS];
     __shared__ int single;
     const int k = blockIdx.x;
     const int t = threadIdx.x;
@@ -1313,39 +1325,39 @@ k_resid_final(phgpu_state st, const double* __restrict__ part, const int32_t* __
     const int64_t C = (nw + XF_THREADS - 1) / XF_THREADS;
     const int64_t w0 = (int64_t)t * C, w1 = (w0 + C < nw) ? w0 + C : nw;
     int cur = -1, first = -1;
-    double a[RS_NV], a_first[RS_NV];
+    double a[NV], a_first[NV];
 #pragma unroll
-    for (int j = 0; j < RS_NV; ++j) a[j] = a_first[j] = pl_id<MAXMASK>(j);
+    for (int j = 0; j < NV; ++j) a[j] = a_first[j] = pl_id<MAXMASK>(j);
     for (int64_t w = w0; w < w1; ++w) {
         const int gnode = node[w * st.nn + k];
-        double p[RS_NV];
+        double p[NV];
 #pragma unroll
-        for (int j = 0; j < RS_NV; ++j) p[j] = part[(w * st.nn + k) * RS_NV + j];
+        for (int j = 0; j < NV; ++j) p[j] = part[(w * st.nn + k) * NV + j];
         if (gnode < 0) continue;
         if (gnode != cur) {
             if (cur >= 0) {
                 if (first < 0) {  // close the chunk's first run
                     first = cur;
 #pragma unroll
-                    for (int j = 0; j < RS_NV; ++j) a_first[j] = a[j];
+                    for (int j = 0; j < NV; ++j) a_first[j] = a[j];
                 } else {          // a complete middle run
 #pragma unroll
-                    for (int j = 0; j < RS_NV; ++j) pl_atomic<MAXMASK>(j, &planes[j * half + cur * st.nlen_max + off], a[j]);
+                    for (int j = 0; j < NV; ++j) pl_atomic<MAXMASK>(j, &planes[j * half + cur * st.nlen_max + off], a[j]);
                 }
             }
             cur = gnode;
 #pragma unroll
-            for (int j = 0; j < RS_NV; ++j) a[j] = pl_id<MAXMASK>(j);
+            for (int j = 0; j < NV; ++j) a[j] = pl_id<MAXMASK>(j);
         }
 #pragma unroll
-        for (int j = 0; j < RS_NV; ++j) a[j] = pl_op<MAXMASK>(j, a[j], p[j]);
+        for (int j = 0; j < NV; ++j) a[j] = pl_op<MAXMASK>(j, a[j], p[j]);
     }
     if (t == 0) single = 1;
     if (first < 0) {  // zero or one run in this chunk: it is the first (and last) run
         fnode[t] = cur;
         lnode[t] = -1;
 #pragma unroll
-        for (int j = 0; j < RS_NV; ++j) {
+        for (int j = 0; j < NV; ++j) {
             fv[j][t] = a[j];
             lv[j][t] = pl_id<MAXMASK>(j);
         }
@@ -1353,7 +1365,7 @@ k_resid_final(phgpu_state st, const double* __restrict__ part, const int32_t* __
         fnode[t] = first;
         lnode[t] = cur;
 #pragma unroll
-        for (int j = 0; j < RS_NV; ++j) {
+        for (int j = 0; j < NV; ++j) {
             fv[j][t] = a_first[j];
             lv[j][t] = a[j];
         }
@@ -1366,12 +1378,12 @@ k_resid_final(phgpu_state st, const double* __restrict__ part, const int32_t* __
     __syncthreads();
     if (single) {
 #pragma unroll
-        for (int j = 0; j < RS_NV; ++j) fv[j][t] = pl_op<MAXMASK>(j, fv[j][t], lv[j][t]);
+        for (int j = 0; j < NV; ++j) fv[j][t] = pl_op<MAXMASK>(j, fv[j][t], lv[j][t]);
         __syncthreads();
         for (int o = XF_THREADS / 2; o > 0; o >>= 1) {
             if (t < o) {
 #pragma unroll
-                for (int j = 0; j < RS_NV; ++j) fv[j][t] = pl_op<MAXMASK>(j, fv[j][t], fv[j][t + o]);
+                for (int j = 0; j < NV; ++j) fv[j][t] = pl_op<MAXMASK>(j, fv[j][t], fv[j][t + o]);
             }
             __syncthreads();
         }
@@ -1380,7 +1392,7 @@ k_resid_final(phgpu_state st, const double* __restrict__ part, const int32_t* __
             for (int u = 0; u < XF_THREADS && g0 < 0; ++u) g0 = fnode[u] >= 0 ? fnode[u] : lnode[u];
             if (g0 >= 0) {
 #pragma unroll
-                for (int j = 0; j < RS_NV; ++j) {
+                for (int j = 0; j < NV; ++j) {
                     double* q = &planes[j * half + g0 * st.nlen_max + off];
                     *q = assign ? fv[j][0] : pl_op<MAXMASK>(j, *q, fv[j][0]);
                 }
@@ -1397,20 +1409,20 @@ k_resid_final(phgpu_state st, const double* __restrict__ part, const int32_t* __
             while (p >= 0 && fnode[p] < 0) --p;
             if (p >= 0 && (lnode[p] >= 0 ? lnode[p] : fnode[p]) == g) continue;
         }
-        double sv[RS_NV];
+        double sv[NV];
 #pragma unroll
-        for (int j = 0; j < RS_NV; ++j) sv[j] = side ? lv[j][t] : fv[j][t];
+        for (int j = 0; j < NV; ++j) sv[j] = side ? lv[j][t] : fv[j][t];
         if (side == 1 || lnode[t] < 0) {  // this run reaches the end of the chunk
             for (int u = t + 1; u < XF_THREADS; ++u) {
                 if (fnode[u] < 0) continue;  // empty chunk
                 if (fnode[u] != g) break;
 #pragma unroll
-                for (int j = 0; j < RS_NV; ++j) sv[j] = pl_op<MAXMASK>(j, sv[j], fv[j][u]);
+                for (int j = 0; j < NV; ++j) sv[j] = pl_op<MAXMASK>(j, sv[j], fv[j][u]);
                 if (lnode[u] >= 0) break;    // the run ends inside chunk u
             }
         }
 #pragma unroll
-        for (int j = 0; j < RS_NV; ++j) pl_atomic<MAXMASK>(j, &planes[j * half + g * st.nlen_max + off], sv[j]);
+        for (int j = 0; j < NV; ++j) pl_atomic<MAXMASK>(j, &planes[j * half + g * st.nlen_max + off], sv[j]);
     }
 }
 
@@ -1642,6 +1654,181 @@ k_nonant_closest(phgpu_state st, const double* __restrict__ v, const double* __r
         best[1] = i;
         best[0] = d;
         __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// ------------------------------------------------------------------ gradient rho
+// The cost-proportional rho of mpisppy/utils/gradient.py, find_rho.py and
+// extensions/gradient_extension.py with the dual metric of utils/wtracker.py:134-157
+// (include/phgpu.h phgpu_grad_cost .. phgpu_rho_from_stats): four single passes over at most
+// nn * S doubles.
+#define GR_T 256
+#define GR_ROWS 65535  // grid rows at most (gridDim.y's limit): a kernel with a nonant per row strides over them
+
+// c and q of column j of scenario s in original units: the library's copies, or on a
+// shared-matrix handle words 0 and 1 of the column's per-scenario record (k_sh_fill; every
+// nonant column has one)
+__device__ __forceinline__ void obj_cq(const phgpu_state& st, int j, int64_t s, double& c, double& q) {
+    if (st.shared) {
+        const double* e = st.sk + (size_t)s * (size_t)st.sk_stride + st.sk_PC + 8 * (size_t)st.cmap[j];
+        c = e[0];
+        q = e[1];
+    } else {
+        c = st.c[(size_t)j * (size_t)st.S + (size_t)s];
+        q = st.q[(size_t)j * (size_t)st.S + (size_t)s];
+    }
+}
+
+// gradient.py:65-81 for f(x) = c.x + 1/2 x.diag(q).x: cost[k, s] = -(c + q xn[k, s]), one
+// nonant per grid row
+__global__ void __launch_bounds__(GR_T)
+k_grad_cost(phgpu_state st, const double* __restrict__ xn, double* __restrict__ cost) {
+    const int64_t S = st.S;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int k = blockIdx.y; k < st.nn; k += gridDim.y) {  // (more nonants than grid rows: strided)
+        const int j = st.nonant_col[k];
+        for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < S; s += stride) {
+#pragma clang fp contract(off)  // two roundings, as numpy's c + q * x: no fused multiply-add
+            double c, q;
+            obj_cq(st, j, s, c, q);
+            const double qx = q * xn[IX(k)];
+            cost[IX(k)] = -(c + qx);
+        }
+    }
+}
+
+// A block's threads summed in a fixed order (wave shuffles, then the waves' sums in wave
+// order); the result is thread 0's
+__device__ __forceinline__ double block_sum_fixed(double v, double* red) {
+    v = wave_sum(v);
+    if ((threadIdx.x & (WAVE - 1)) == 0) red[threadIdx.x / WAVE] = v;
+    __syncthreads();
+    double t = 0.0;
+    if (threadIdx.x == 0)
+        for (int u = 0; u < (int)(blockDim.x / WAVE); ++u) t += red[u];
+    return t;
+}
+
+// wtracker.py:141-154: out[0] = scale x sum over the local (k, s) of |W - W_prev|, and W_prev
+// = W in the same pass.  Every thread adds its elements in index order, every block its threads
+// in a fixed order; the block's sum is swapped into bpart and the block with the last ticket
+// adds the blocks' sums in block order and stores out (k_nonant_closest's exchange / ticket
+// chain): the same bits on every run.  The grid has at most WD_BLOCKS blocks.
+#define WD_BLOCKS 256
+__global__ void __launch_bounds__(GR_T)
+k_w_diff(const double* __restrict__ W, double* __restrict__ W_prev, int64_t tot, double scale,
+         double* __restrict__ bpart, int32_t* __restrict__ cnt, double* __restrict__ out) {
+    __shared__ double red[GR_T / WAVE];
+    __shared__ double fin[WD_BLOCKS];
+    __shared__ int last;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += stride) {
+        const double w = W[i];
+        acc += fabs(w - W_prev[i]);
+        W_prev[i] = w;
+    }
+    const double b = block_sum_fixed(acc, red);
+    const int nblk = (int)gridDim.x;
+    if (threadIdx.x == 0) {
+        const double o0 = __hip_atomic_exchange(&bpart[blockIdx.x], b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // the swap has returned before the ticket is taken (see conv_last_block)
+        asm volatile("" ::"v"(o0) : "memory");
+        const int tk = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last = tk == nblk - 1;
+    }
+    __syncthreads();
+    if (!last) return;
+    for (int u = threadIdx.x; u < WD_BLOCKS; u += blockDim.x)
+        fin[u] = u < nblk ? __hip_atomic_fetch_add(&bpart[u], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+    __syncthreads();
+    for (int o = WD_BLOCKS / 2; o > 0; o >>= 1) {
+        for (int u = threadIdx.x; u < o; u += blockDim.x) fin[u] += fin[u + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out[0] = scale * fin[0];
+        __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// find_rho.py:170-203 up to the order statistic, for a two-stage handle: r[k, s] = |cost[k, s]|
+// / denominator and, per nonant, the per-wave partials of sum r, max(-r) and max(r) for
+// k_resid_final<0x6, 3> (every wave's scenarios share the one node).  One lane per scenario.
+//   gden == null: the scenario's own denominator, the largest over its nonants j of
+//     max(|x_j - x̄_j|, 2 (x_j - x̄_j)^2): np.max((w_denom, prox_denom)) at find_rho.py:189
+//     is ONE scalar per scenario (:78-115);
+//   gden given:   gden[offset of k] for every scenario (_grad_denom, :118-147).
+// IEEE division (numpy's): a zero denominator gives +inf (0 / 0 NaN, which fmax drops).
+#define RR_NV 3  // planes: sum r, max(-r), max(r)
+__global__ void __launch_bounds__(BLOCK)
+k_rho_ratio_partial(phgpu_state st, const double* __restrict__ cost, const double* __restrict__ x,
+                    const double* __restrict__ xbar, const double* __restrict__ gden) {
+    const int64_t S = st.S;
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t wave = s / WAVE;
+    const bool act = s < S;
+    const int nn = st.nn;
+    double d = 0.0;
+    if (!gden && act) {
+        for (int k = 0; k < nn; ++k) {
+            const double dx = x[IX(st.nonant_col[k])] - xbar[IX(k)];
+            d = fmax(d, fmax(fabs(dx), 2.0 * (dx * dx)));
+        }
+    }
+    const int g0 = __shfl(act ? st.node_of[s] : 0, 0, WAVE);
+    for (int k = 0; k < nn; ++k) {
+        double r = 0.0;
+        if (act) r = fabs(cost[IX(k)]) / (gden ? gden[st.nonant_off[k]] : d);
+        const double sum = wave_sum(r);
+        const double mn = wave_max(act ? -r : -INFINITY);
+        const double mx = wave_max(act ? r : -INFINITY);
+        if ((threadIdx.x & (WAVE - 1)) == 0) {
+            double* p = &st.rr_part[(wave * nn + k) * RR_NV];
+            p[0] = sum;
+            p[1] = mn;
+            p[2] = mx;
+            st.rr_node[wave * nn + k] = g0;
+        }
+    }
+}
+
+// the planes of phgpu_rho_ratio_stats an entry without a nonant keeps: 0, -inf, -inf
+__global__ void __launch_bounds__(256) k_rr_clear(double* __restrict__ planes, int64_t half) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < RR_NV * half; i += stride)
+        planes[i] = i < half ? 0.0 : -INFINITY;
+}
+
+// find_rho.py:150-168 (_order_stat) and the rho rewrite of gradient_extension.py:85-94 for a
+// two-stage handle: every local rho[k, s] becomes the order statistic of nonant k's ratios,
+// if the gate is open -- |(prev - cur) / prev| <= thr on gate = {prev, cur}, which NaN and
+// inf fail (gradient_extension.py:65-68); a null gate is open.  Every thread evaluates the
+// gate itself (two cached loads); a closed gate stores nothing to rho.  One nonant per grid
+// row; applied (may be null) is stored by the grid's first thread.
+__global__ void __launch_bounds__(GR_T)
+k_rho_from_stats(phgpu_state st, const double* __restrict__ planes, double s_total, double alpha,
+                 const double* __restrict__ gate, double thr, double* __restrict__ rho,
+                 int32_t* __restrict__ applied) {
+    const int64_t S = st.S;
+    bool open = true;
+    if (gate) {
+        const double prev = gate[0], cur = gate[1];
+        open = fabs((prev - cur) / prev) <= thr;
+    }
+    if (applied && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *applied = open ? 1 : 0;
+    if (!open) return;
+    const int64_t half = (int64_t)st.num_nodes * st.nlen_max;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int k = blockIdx.y; k < st.nn; k += gridDim.y) {  // (more nonants than grid rows: strided)
+        const int off = st.nonant_off[k];
+        const double mean = planes[off] / s_total;
+        const double mn = -planes[half + off], mx = planes[2 * half + off];
+        double v;
+        if (alpha == 0.5) v = mean;
+        else if (alpha < 0.5) v = mn + alpha * 2.0 * (mean - mn);
+        else v = (2.0 * mean - mx) + alpha * 2.0 * (mx - mean);
+        for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < S; s += stride) rho[IX(k)] = v;
     }
 }
 
@@ -3917,6 +4104,104 @@ extern "C" int phgpu_nonant_closest(phgpu_handle h, const double* v, const doubl
     return 0;
 }
 
+// utils/gradient.py:65-81
+extern "C" int phgpu_grad_cost(phgpu_handle h, const double* xn, double* cost, void* stream) {
+    if (!h || !xn || !cost) return set_err(-1, "null argument");
+    if (!h->scen_set) return set_err(-1, "phgpu_grad_cost: no scenario data yet");
+    FLUSH_STEP(h);
+    if (h->nn == 0) return 0;
+    const int64_t bx = std::min<int64_t>((h->S + GR_T - 1) / GR_T, 65535);
+    hipLaunchKernelGGL(k_grad_cost, dim3((unsigned)bx, (unsigned)std::min(h->nn, GR_ROWS)), dim3(GR_T), 0,
+                       (hipStream_t)stream, *h, xn, cost);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// utils/wtracker.py:141-154
+extern "C" int phgpu_w_diff(phgpu_handle h, const double* W, double* W_prev, double* out, void* stream) {
+    if (!h || !W || !W_prev || !out) return set_err(-1, "null argument");
+    FLUSH_STEP(h);
+    hipStream_t st = (hipStream_t)stream;
+    if (h->nn == 0) {
+        HIPCHK(hipMemsetAsync(out, 0, sizeof(double), st));
+        return 0;
+    }
+    if (!h->wd_part) {  // first use: the block sums and the (zeroed) last-block counter
+        int rc = dalloc(h, &h->wd_part, (size_t)WD_BLOCKS);
+        if (!rc) rc = dalloc(h, &h->wd_cnt, 1);
+        if (rc) {
+            if (h->wd_part) (void)hipFree(h->wd_part);
+            h->wd_part = nullptr;
+            return rc;
+        }
+        HIPCHK(hipMemsetAsync(h->wd_cnt, 0, sizeof(int32_t), st));
+    }
+    const int64_t tot = (int64_t)h->nn * h->S;
+    // four elements per thread before the grid is capped
+    const int64_t nblk = std::max<int64_t>(1, std::min<int64_t>((tot + 4 * GR_T - 1) / (4 * GR_T), WD_BLOCKS));
+    hipLaunchKernelGGL(k_w_diff, dim3((unsigned)nblk), dim3(GR_T), 0, st, W, W_prev, tot, 1.0 / (double)tot,
+                       h->wd_part, h->wd_cnt, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int two_stage_only(phgpu_state* h, const char* who) {
+    if (h->depth != 1 || h->num_nodes != 1)
+        return set_err(-3, "%s: two-stage handles only (depth %d, %d nodes)", who, h->depth, h->num_nodes);
+    return 0;
+}
+
+// utils/find_rho.py:78-147 and 170-203
+extern "C" int phgpu_rho_ratio_stats(phgpu_handle h, const double* cost, const double* x, const double* xbar,
+                                     const double* gden, double* planes, void* stream) {
+    if (!h || !cost || !planes || (!gden && (!x || !xbar))) return set_err(-1, "null argument");
+    if (two_stage_only(h, "phgpu_rho_ratio_stats")) return -3;
+    FLUSH_STEP(h);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t half = (int64_t)h->num_nodes * h->nlen_max;
+    const int assign = h->nlen_max == h->nn ? 1 : 0;
+    if (!assign) {
+        hipLaunchKernelGGL(k_rr_clear, dim3((unsigned)std::min<int64_t>((RR_NV * half + 255) / 256, 256)), dim3(256),
+                           0, st, planes, half);
+        HIPCHK(hipGetLastError());
+    }
+    if (h->nn == 0) return 0;
+    if (!h->rr_part) {  // first use: workspace of its own
+        const size_t cnt = (size_t)h->nwaves * (size_t)h->nn;
+        int rc = dalloc(h, &h->rr_part, cnt * RR_NV);
+        if (!rc) rc = dalloc(h, &h->rr_node, cnt);
+        if (rc) {
+            if (h->rr_part) (void)hipFree(h->rr_part);
+            h->rr_part = nullptr;
+            return rc;
+        }
+    }
+    hipLaunchKernelGGL(k_rho_ratio_partial, grid_for(h->S), dim3(BLOCK), 0, st, *h, cost, x, xbar, gden);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL((k_resid_final<0x6, RR_NV>), dim3(h->nn), dim3(XF_THREADS), 0, st, *h,
+                       (const double*)h->rr_part, (const int32_t*)h->rr_node, planes, assign);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// utils/find_rho.py:150-168, extensions/gradient_extension.py:65-68 and 85-94
+extern "C" int phgpu_rho_from_stats(phgpu_handle h, const double* planes, int64_t S_total, double order_stat,
+                                    const double* gate, double thr, double* rho, int32_t* applied, void* stream) {
+    if (!h || !planes || !rho) return set_err(-1, "null argument");
+    if (!(order_stat >= 0.0 && order_stat <= 1.0))
+        return set_err(-1, "phgpu_rho_from_stats: order_stat %g is not in [0, 1] (0 the min, 0.5 the mean, 1 the max)",
+                       order_stat);
+    if (S_total <= 0) return set_err(-1, "phgpu_rho_from_stats: S_total %lld", (long long)S_total);
+    if (two_stage_only(h, "phgpu_rho_from_stats")) return -3;
+    FLUSH_STEP(h);
+    const int64_t bx = std::min<int64_t>((h->S + GR_T - 1) / GR_T, std::max<int64_t>(1, UPD_BLOCKS / std::max(1, h->nn)));
+    const unsigned rows = (unsigned)std::min(std::max(1, h->nn), GR_ROWS);
+    hipLaunchKernelGGL(k_rho_from_stats, dim3((unsigned)bx, rows), dim3(GR_T), 0,
+                       (hipStream_t)stream, *h, planes, (double)S_total, order_stat, gate, thr, rho, applied);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 extern "C" int phgpu_expectations(phgpu_handle h, const double* obj, const double* bound,
                                   const int32_t* status, double* out, void* stream) {
     if (!h || !obj || !bound || !status || !out) return set_err(-1, "null argument");
@@ -4000,7 +4285,8 @@ extern "C" int phgpu_destroy(phgpu_handle h) {
     {
         void* more[] = {h->xp[0], h->xp[1], h->xp_node[0], h->xp_node[1], h->xp_dirty[0], h->xp_dirty[1],
                         h->cpart_blk, h->blk_cnt, h->nb_idx, h->rs_part, h->rs_node,
-                        h->ns_part, h->ns_node, h->nc_part, h->nc_cnt};
+                        h->ns_part, h->ns_node, h->nc_part, h->nc_cnt, h->wd_part, h->wd_cnt,
+                        h->rr_part, h->rr_node};
         for (void* p : more)
             if (p) (void)hipFree(p);
     }

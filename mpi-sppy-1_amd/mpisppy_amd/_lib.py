@@ -65,7 +65,8 @@ EXPORTS = ["phgpu_default_options", "phgpu_create", "phgpu_create2", "phgpu_set_
            "phgpu_set_nonant_probs", "phgpu_set_ipm_tuning", "phgpu_ipm_prof",
            "phgpu_ph_loop", "phgpu_stream_info", "phgpu_comm_unique_id", "phgpu_comm_init",
            "phgpu_allreduce_sum", "phgpu_ph_residuals", "phgpu_norm_rho_update",
-           "phgpu_nonant_stats", "phgpu_nonant_closest"]
+           "phgpu_nonant_stats", "phgpu_nonant_closest", "phgpu_grad_cost", "phgpu_w_diff",
+           "phgpu_rho_ratio_stats", "phgpu_rho_from_stats"]
 
 _lib = None
 
@@ -119,6 +120,10 @@ def load(path=None):
                                           c_vp]
     lib.phgpu_nonant_stats.argtypes = [c_vp, c_vp, c_vp, c_vp]
     lib.phgpu_nonant_closest.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
+    lib.phgpu_grad_cost.argtypes = [c_vp, c_vp, c_vp, c_vp]
+    lib.phgpu_w_diff.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp]
+    lib.phgpu_rho_ratio_stats.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
+    lib.phgpu_rho_from_stats.argtypes = [c_vp, c_vp, c_i64, c_dbl, c_vp, c_dbl, c_vp, c_vp, c_vp]
     lib.phgpu_ipm_info.argtypes = [c_vp, ctypes.POINTER(c_dbl)]
     lib.phgpu_ipm_prof.argtypes = [c_vp, ctypes.POINTER(ctypes.c_ulonglong), c_i64]
     lib.phgpu_ipm_prof.restype = c_i64

@@ -12,6 +12,10 @@ GPU, scenario-fastest ``[k, S]``) and sequences the per-PH-iteration work:
     xhat candidates -> phgpu_nonant_stats + SUM / MAX all-reduces, phgpu_nonant_closest
                                                        (extensions/xhatxbar.py, xhatclosest.py,
                                                         cylinders/slam_heuristic.py)
+    gradient rho    -> phgpu_grad_cost, phgpu_w_diff + all-reduce, phgpu_rho_ratio_stats +
+                       SUM / MAX all-reduces + phgpu_rho_from_stats
+                                                       (utils/gradient.py, find_rho.py, wtracker.py,
+                                                        extensions/gradient_extension.py)
 
 All launches go to torch's current stream; host synchronisation happens only where
 the reference needs a host scalar (the convergence test, bounds).
@@ -131,7 +135,8 @@ class PHEngine:
                       "allreduce_xbar": 0, "allreduce_conv_side": 0, "allreduce_conv_main": 0, "xbar_ahead_used": 0,
                       "ph_loop": 0, "ph_residuals": 0, "norm_rho_update": 0, "allreduce_resid": 0,
                       "solve_deferred": 0, "nonant_stats": 0, "nonant_closest": 0, "allreduce_stats_sum": 0,
-                      "allreduce_stats_max": 0}
+                      "allreduce_stats_max": 0, "grad_cost": 0, "w_diff": 0, "rho_ratio_stats": 0,
+                      "rho_from_stats": 0, "allreduce_wdiff": 0, "allreduce_ratio_sum": 0, "allreduce_ratio_max": 0}
         # several ranks: the conv all-reduce on a side stream under the next solve (False: on
         # the launch stream ahead of it -- bench.py --no-conv-overlap, the comparison case)
         self.overlap_conv = True
@@ -816,6 +821,119 @@ class PHEngine:
         li = torch.tensor([float(i) if win == self.comm.rank else -1.0], dtype=torch.float64, device=self.device)
         self.comm.allreduce_max_(li)
         return gmin, win, int(li.item())
+
+    # -------------------------------------------------------------- gradient rho
+    def grad_cost(self, xn):
+        """The gradient cost at the nonant values ``xn`` (device [nn, S], the layout of W):
+        cost[k, s] = -(c + q xn) of the stored objective (phgpu_grad_cost; Find_Grad.compute_grad,
+        gradient.py:65-81, without its solve).  Returns the device [nn, S] tensor ``gcost``."""
+        self._flush_step()
+        if getattr(self, "gcost", None) is None:
+            self.gcost = torch.zeros_like(self.W)
+        xn = self._nonant_arg(xn)
+        self.calls["grad_cost"] += 1
+        _lib.check(self.lib.phgpu_grad_cost(self.h, _ptr(xn), _ptr(self.gcost), self._stream()), "phgpu_grad_cost")
+        return self.gcost
+
+    def w_diff(self):
+        """WTracker.W_diff (wtracker.py:134-157, phgpu_w_diff): the mean |W - W_prev| over all
+        scenarios and nonants of all ranks.  THIS DEPARTS FROM wtracker.py:155-157 with several
+        ranks: the reference sums the ranks' own means and divides by n_proc, which depends on
+        how the scenarios are split unless every rank holds equally many; here every rank's mean
+        is weighted by its share of the scenarios (the same number for an even split).  W_prev
+        (owned here; W at the first call, which therefore gives 0 as the reference's
+        local_Ws[-1] = local_Ws[0]) renewed in the same pass.  Device work only: every call's
+        value is appended to the device history ``w_hist`` (entry 0 is 0), and the returned
+        double[2] view ``w_gate`` = {the previous call's value, this one's} is the gate of
+        ``find_rho`` -- no copy between calls.  ``w_diff_value`` reads the last one back."""
+        self._flush_step()
+        if getattr(self, "w_hist", None) is None:
+            self.w_hist = torch.zeros(1024, dtype=torch.float64, device=self.device)
+            self._w_n = 0
+            self._W_prev = self.W.clone()
+        self._w_n += 1
+        if self._w_n >= self.w_hist.numel():
+            self.w_hist = torch.cat([self.w_hist, torch.zeros_like(self.w_hist)])
+        cur = self.w_hist[self._w_n:self._w_n + 1]
+        self.calls["w_diff"] += 1
+        _lib.check(self.lib.phgpu_w_diff(self.h, _ptr(self.W), _ptr(self._W_prev), _ptr(cur), self._stream()),
+                   "phgpu_w_diff")
+        if self.comm.size > 1:
+            # the mean over ALL scenarios: every rank's mean weighted by its share of them.  The
+            # reference divides the sum of the ranks' means by n_proc (wtracker.py:155-157), which
+            # is the same number when the ranks hold equally many scenarios and depends on the
+            # split when they do not
+            cur.mul_(float(self.S) / float(self.total_scenarios()))
+            self.calls["allreduce_wdiff"] += 1
+            self._ar(cur)
+        self.w_gate = self.w_hist[self._w_n - 1:self._w_n + 1]
+        return self.w_gate
+
+    def w_diff_value(self):
+        """Host value of the last ``w_diff`` (one small read back)."""
+        return float(self.w_hist[self._w_n].item())
+
+    def w_diff_history(self):
+        """Host array of every ``w_diff`` so far, in call order."""
+        return self.w_hist[1:self._w_n + 1].cpu().numpy()
+
+    def total_scenarios(self):
+        """Scenarios of all ranks (one all-reduce and read back at the first call)."""
+        if getattr(self, "_S_total", None) is None:
+            t = torch.tensor([float(self.S)], dtype=torch.float64, device=self.device)
+            if self.comm.size > 1:
+                self.comm.allreduce_sum_(t)
+            self._S_total = int(round(t.item()))
+        return self._S_total
+
+    def rho_ratio_stats(self, cost, indep_denom=False, rel_bound=1e3):
+        """Per nonant, the sum, -min and max over all scenarios of |cost| / denominator
+        (phgpu_rho_ratio_stats; Find_Rho.compute_rho, find_rho.py:170-203, up to the order
+        statistic) for the current x and x̄: a device [3, num_nodes, nlen_max] tensor, reduced
+        over the ranks by one SUM and one MAX all-reduce.  ``indep_denom``: the scenario-
+        independent denominator max(1 / rel_bound, sum_s prob_coeff |x - x̄|) of _grad_denom
+        (:118-147), which is plane 1 of ``residuals``; else every scenario's own.  Two-stage
+        only (PhgpuError rc=-3 otherwise).  Device work only."""
+        self._flush_xbar()
+        half = self.num_nodes * self.nlen_max
+        if getattr(self, "rr_planes", None) is None:
+            self.rr_planes = torch.empty(3 * half, dtype=torch.float64, device=self.device)
+        cost = self._nonant_arg(cost)
+        gden = None
+        if indep_denom:
+            self.residuals()
+            gden = torch.clamp(self.resid[half:2 * half], min=1.0 / float(rel_bound))
+        self.gden = gden
+        self.calls["rho_ratio_stats"] += 1
+        _lib.check(self.lib.phgpu_rho_ratio_stats(self.h, _ptr(cost), _ptr(self.x), _ptr(self.xbar), _ptr(gden),
+                                                  _ptr(self.rr_planes), self._stream()), "phgpu_rho_ratio_stats")
+        if self.comm.size > 1:
+            self.calls["allreduce_ratio_sum"] += 1
+            self._ar(self.rr_planes[:half])
+            self.calls["allreduce_ratio_max"] += 1
+            self.comm.allreduce_max_(self.rr_planes[half:])
+        return self.rr_planes.view(3, self.num_nodes, self.nlen_max)
+
+    def find_rho(self, cost, order_stat, indep_denom=False, rel_bound=1e3, gate=None, thr=0.05, applied=None):
+        """rho[k, s] = the order statistic ``order_stat`` (0 the min, 0.5 the mean, 1 the max;
+        Find_Rho._order_stat, find_rho.py:150-168) of nonant k's ratios |cost| / denominator
+        over all scenarios, for every local scenario (``rho_ratio_stats`` +
+        phgpu_rho_from_stats).  ``gate``: a device double[2] tensor {previous, current} dual
+        metric (``w_diff``'s ``w_gate``), rho being rewritten only if it moved by at most
+        ``thr`` relative (gradient_extension.py:65-68), or None: always.  ``applied``: a device
+        int32[1] tensor that receives 1 / 0 (default ``rho_applied``).  Device work only."""
+        self.rho_ratio_stats(cost, indep_denom, rel_bound)
+        if getattr(self, "rho_applied", None) is None:
+            self.rho_applied = torch.zeros(1, dtype=torch.int32, device=self.device)
+        applied = self.rho_applied if applied is None else applied
+        self.calls["rho_from_stats"] += 1
+        _lib.check(self.lib.phgpu_rho_from_stats(self.h, _ptr(self.rr_planes), self.total_scenarios(),
+                                                 float(order_stat), _ptr(gate), float(thr), _ptr(self.rho),
+                                                 _ptr(applied), self._stream()), "phgpu_rho_from_stats")
+
+    def rho_ratio_planes(self):
+        """Host [3, num_nodes * nlen_max] copy of the planes of the last ``rho_ratio_stats``."""
+        return self.rr_planes.cpu().numpy().reshape(3, -1)
 
     def convergence_diff(self):
         """phbase.py:330-343: sum over ranks of per-rank means, / n_proc (host float)."""

@@ -17,6 +17,8 @@ from ..cylinders.xhatshufflelooper_bounder import XhatShuffleInnerBound
 from ..convergers.norm_rho_converger import NormRhoConverger
 from ..convergers.primal_dual_converger import PrimalDualConverger
 from ..extensions.extension import MultiExtension
+from ..extensions.gradient_extension import Gradient_extension
+from ..extensions.mult_rho_updater import MultRhoUpdater
 from ..extensions.norm_rho_updater import NormRhoUpdater
 from ..opt.ph import PH
 from ..phbase import PHBase
@@ -220,6 +222,37 @@ def add_norm_rho_updater(hub_dict, cfg):
     if _get(cfg, "use_norm_rho_updater", False):
         hub_dict = extension_adder(hub_dict, NormRhoUpdater)
         hub_dict["opt_kwargs"]["options"]["norm_rho_options"] = dict(_get(cfg, "norm_rho_options", {}))
+    return hub_dict
+
+
+# examples/farmer/farmer_rho_demo.py:100-120 (cfg.rho_setter -> Gradient_extension with
+# gradient_extension_options = {'cfg': cfg}; config.py:613-658 gradient_args / rho_args:
+# order_stat, rho_relative_bound, xhatpath).  The flag is cfg.grad_rho_setter or the
+# reference's cfg.rho_setter; the options are copied into a dict, and since cost and rho stay
+# on the device there are no file names among them
+def add_gradient_rho(hub_dict, cfg):
+    if _get(cfg, "grad_rho_setter", False) or _get(cfg, "rho_setter", False) is True:
+        hub_dict = extension_adder(hub_dict, Gradient_extension)
+        o = dict(_get(cfg, "gradient_extension_options", {}))
+        for name, default in (("order_stat", None), ("rho_relative_bound", 1e3), ("xhatpath", None), ("xhat", None),
+                              ("indep_denom", False), ("dual_update_threshold", 0.05)):
+            if name not in o and _get(cfg, name, default) is not None:
+                o[name] = _get(cfg, name, default)
+        hub_dict["opt_kwargs"]["options"]["gradient_extension_options"] = o
+    return hub_dict
+
+
+# examples/farmer/farmer_cylinders.py (cfg.mult_rho -> MultRhoUpdater with
+# cfg.mult_rho_to_dict(), config.py:487-516); a cfg without that method gives its
+# mult_rho_* attributes or a ready ``mult_rho_options`` dict
+def add_mult_rho_updater(hub_dict, cfg):
+    if _get(cfg, "mult_rho", False):
+        hub_dict = extension_adder(hub_dict, MultRhoUpdater)
+        o = dict(_get(cfg, "mult_rho_options", {}))
+        for name in ("convergence_tolerance", "rho_update_stop_iteration", "rho_update_start_iteration"):
+            if name not in o and getattr(cfg, "mult_rho_" + name.replace("rho_", "", 1), None) is not None:
+                o[name] = getattr(cfg, "mult_rho_" + name.replace("rho_", "", 1))
+        hub_dict["opt_kwargs"]["options"]["mult_rho_options"] = o
     return hub_dict
 
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""PH iterations and time to convergence with fixed rho and with NormRhoUpdater.
+"""PH iterations and time to convergence with fixed rho and with the rho extensions.
 
 Config 3 (farmer, 65,536 scenarios, cm = 1, rho = 1) from Iter0 to conv < convthresh:
 
@@ -10,13 +10,19 @@ Config 3 (farmer, 65,536 scenarios, cm = 1, rho = 1) from Iter0 to conv < convth
   noop         an extension whose miditer does nothing on the host: the non-speculative
                loop, i.e. what any miditer extension cost before miditer_on_device
   updater-host NormRhoUpdater with the speculative solve turned off
+  gradient     Gradient_extension: the cost-proportional rho (order_stat 0.5, scenario-
+               dependent denominators), rewritten on the device when W_diff stalls; the
+               speculative loop
+  mult         MultRhoUpdater with the reference's default options: a host miditer, so the
+               non-speculative loop
 
 and, with --kernels, the HIP-event time of phgpu_ph_residuals and phgpu_norm_rho_update
 next to phgpu_ph_update_ex on the same engine.  Prints one line per mode: PH iterations,
 wall seconds of iterk_loop, mean ms per PH iteration, the final conv and rho range.
 
     python tools/rho_convergence.py [--scens 65536] [--convthresh 1e-3] [--limit 3000]
-                                    [--modes fixed,updater,noop,updater-host] [--kernels]
+                                    [--modes fixed,updater,noop,updater-host,gradient,mult] [--kernels]
+                                    [--order-stat 0.5] [--indep-denom]
 """
 import argparse
 import json
@@ -30,9 +36,11 @@ for p in (os.path.join(ROOT, "mpi-sppy-1_amd"), ROOT):
         sys.path.insert(0, p)
 
 
-def make_ph(mode, S, thresh, limit, norm_rho_options):
+def make_ph(mode, S, thresh, limit, norm_rho_options, grad_options=None):
     from mpisppy_amd.examples import farmer
     from mpisppy_amd.extensions.extension import Extension
+    from mpisppy_amd.extensions.gradient_extension import Gradient_extension
+    from mpisppy_amd.extensions.mult_rho_updater import MultRhoUpdater
     from mpisppy_amd.extensions.norm_rho_updater import NormRhoUpdater
     from mpisppy_amd.opt.ph import PH
 
@@ -40,18 +48,21 @@ def make_ph(mode, S, thresh, limit, norm_rho_options):
         def miditer(self):
             pass
 
-    ext = {"fixed": None, "updater": NormRhoUpdater, "noop": NoopMiditer, "updater-host": NormRhoUpdater}[mode]
+    ext = {"fixed": None, "updater": NormRhoUpdater, "noop": NoopMiditer, "updater-host": NormRhoUpdater,
+           "gradient": Gradient_extension, "mult": MultRhoUpdater}[mode]
     opts = {"solver_name": "mi355x_pdhg", "PHIterLimit": limit, "defaultPHrho": 1.0, "convthresh": thresh,
             "verbose": False, "display_progress": False, "toc": False, "device": "cuda:0",
             "batch_creator": farmer.batch_creator, "iterk_solver_options": dict(farmer.PDHG_ITERK_OPTIONS),
-            "speculative_solve": mode != "updater-host", "norm_rho_options": dict(norm_rho_options)}
+            "speculative_solve": mode != "updater-host", "norm_rho_options": dict(norm_rho_options),
+            "gradient_extension_options": dict(grad_options or {"order_stat": 0.5})}
     return PH(opts, farmer.scenario_names_creator(S), farmer.scenario_creator, extensions=ext,
               scenario_creator_kwargs={"crops_multiplier": 1, "num_scens": S})
 
 
 def run_mode(mode, a, norm_rho_options):
     import torch
-    ph = make_ph(mode, a.scens, a.convthresh, a.limit, norm_rho_options)
+    ph = make_ph(mode, a.scens, a.convthresh, a.limit, norm_rho_options,
+                 {"order_stat": a.order_stat, "indep_denom": a.indep_denom})
     ph.PH_Prep()
     ph.Iter0()
     torch.cuda.synchronize()
@@ -68,8 +79,14 @@ def run_mode(mode, a, norm_rho_options):
            "calls": {k: v for k, v in e.calls.items() if v}}
     if mode.startswith("updater") and e.calls["norm_rho_update"]:
         res["last_counts"] = e.norm_rho_counts().tolist()
+    if mode == "gradient":
+        res["rho_update_iterations"] = ph.extobject.rho_update_iterations()
+    if mode == "mult":
+        res["rho_update_iterations"] = list(ph.extobject.acted)
     if a.kernels and mode == "updater":
         res["kernel_us"] = kernel_times(e, ph)
+    if a.kernels and mode == "gradient":
+        res["kernel_us"] = grad_kernel_times(e, ph)
     e.close()
     return res
 
@@ -108,6 +125,27 @@ def kernel_times(e, ph, reps=200):
     return out
 
 
+def grad_kernel_times(e, ph, reps=200):
+    """Mean HIP-event microseconds per call of engine.w_diff and engine.find_rho (the ratio pass,
+    its final sum and the rule, gate closed so rho stays) on this engine's current state."""
+    import torch
+    cost = ph.extobject.grad_object.cost
+    shut = torch.tensor([0.0, 1.0], dtype=torch.float64, device=e.device)
+    out = {}
+    for name, fn in (("w_diff", e.w_diff), ("find_rho", lambda: e.find_rho(cost, 0.5, gate=shut)),
+                     ("grad_cost", lambda: e.grad_cost(e.xbar))):
+        for _ in range(10):
+            fn()
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+        for _ in range(reps):
+            fn()
+        ev[1].record()
+        ev[1].synchronize()
+        out[name] = 1e3 * ev[0].elapsed_time(ev[1]) / reps
+    return out
+
+
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--scens", type=int, default=65536)
@@ -116,6 +154,8 @@ def main():
     p.add_argument("--modes", default="fixed,updater,noop,updater-host")
     p.add_argument("--kernels", action="store_true", help="time the new launches next to the update kernel")
     p.add_argument("--norm-rho-option", action="append", default=[], metavar="KEY=VALUE")
+    p.add_argument("--order-stat", type=float, default=0.5, help="gradient mode: 0 the min, 0.5 the mean, 1 the max")
+    p.add_argument("--indep-denom", action="store_true", help="gradient mode: the scenario-independent denominator")
     a = p.parse_args()
     nro = {}
     for kv in a.norm_rho_option:

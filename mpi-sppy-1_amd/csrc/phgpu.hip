@@ -68,6 +68,10 @@ static int set_err(int code, const char* fmt, ...) {
 // ------------------------------------------------------------------ state
 struct jit_module;  // solve_jit.inc: the hipRTC-compiled path-5 kernel of a handle
 struct ipm_module;  // solve_ipm.inc: the hipRTC-compiled path-6 module of a handle
+struct ph_ws {      // a reduction's device workspace: partials, and node tags or a ticket counter
+    double* part;
+    int32_t* tag;
+};
 
 struct phgpu_state {
     int device;
@@ -229,25 +233,14 @@ struct phgpu_state {
     int fuse_now;      // ipm_launch folds pend into this launch
     int64_t folded;    // PH steps folded into solve launches so far (phgpu_ipm_info)
     int32_t* nb_idx;   // [nn] node_buf index (node of the local scenarios, offset) of nonant k (two-stage)
-    // phgpu_ph_residuals' own per-wave partials [nwaves * nn * 4] and node tags [nwaves * nn],
-    // allocated at its first call (part / part_node may belong to a deferred step or to the
-    // path-6 epilogue)
-    double* rs_part;
-    int32_t* rs_node;
-    // phgpu_nonant_stats' per-wave partials and node tags (the same shapes) and
-    // phgpu_nonant_closest's per-block (distance, index) pairs [2 * blocks] and last-block
-    // counter, each allocated at the entry's first call
-    double* ns_part;
-    int32_t* ns_node;
-    double* nc_part;
-    int32_t* nc_cnt;
-    // phgpu_w_diff's per-block partials [WD_BLOCKS] and last-block counter, and
-    // phgpu_rho_ratio_stats' per-wave partials [nwaves * nn * 3] and node tags [nwaves * nn],
-    // each allocated at the entry's first call
-    double* wd_part;
-    int32_t* wd_cnt;
-    double* rr_part;
-    int32_t* rr_node;
+    // Reduction workspaces, each its entry point's own and allocated at that entry's first call
+    // (part / part_node may belong to a deferred step or to the path-6 epilogue; separate
+    // allocations, so that calls on different streams may overlap).  Per-wave partials
+    // [nwaves * nn * planes] with node tags [nwaves * nn]: rs phgpu_ph_residuals (4 planes), ns
+    // phgpu_nonant_stats (4), rr phgpu_rho_ratio_stats (3).  Per-block partials with a
+    // last-block counter as tag[0]: nc phgpu_nonant_closest ((distance, index) pairs
+    // [2 * blocks]), wd phgpu_w_diff ([WD_BLOCKS]).
+    ph_ws rs, ns, nc, wd, rr;
 };
 
 #define IX(k) ((size_t)(k) * (size_t)S + (size_t)s)
@@ -1016,1093 +1009,8 @@ __global__ void k_stats_copy(const unsigned long long* __restrict__ src, int cop
 #include "solve_ipm.inc"
 
 // ------------------------------------------------------------------ PH reductions
-// phbase.py:54-79: per-wave partial sums of prob_coeff * x and prob_coeff * x^2 for
-// each nonant; a wave whose scenarios share one node at that depth writes one
-// partial (deterministic); a mixed wave adds per lane with fp64 atomics.
-__global__ void __launch_bounds__(BLOCK)
-k_xbar_partial(phgpu_state st, const double* __restrict__ x, double* __restrict__ node_buf, int clear) {
-    const int64_t S = st.S;
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t wave = s / WAVE;
-    const bool act = s < S;
-    const int half = st.num_nodes * st.nlen_max;
-    // no wave spans two nodes (st.xbar_mixed == 0): this kernel does not touch node_buf
-    // below, so it clears it for k_xbar_final (one launch less than a memset)
-    if (clear && blockIdx.y == 0)
-        for (int64_t i = s; i < 2 * (int64_t)half; i += (int64_t)gridDim.x * blockDim.x) node_buf[i] = 0.0;
-    // one nonant per grid row (blockIdx.y; see k_ph_update)
-    if ((int)blockIdx.y < st.nn) {
-        const int k = blockIdx.y;
-        const int d = st.nonant_depth[k];
-        const int gnode = act ? st.node_of[IX(d)] : -1;
-        const double w = act ? (st.pvar ? st.pvar[IX(k)] : st.pcoef[IX(d)]) : 0.0;
-        const double v = act ? x[IX(st.nonant_col[k])] : 0.0;
-        const int g0 = __shfl(gnode, 0, WAVE);
-        const bool uniform = !__any(act && gnode != g0);
-        if (uniform) {
-            const double a = wave_sum(w * v);
-            const double b = wave_sum(w * v * v);
-            if ((threadIdx.x & (WAVE - 1)) == 0) {
-                st.part[(wave * st.nn + k) * 2 + 0] = a;
-                st.part[(wave * st.nn + k) * 2 + 1] = b;
-                st.part_node[wave * st.nn + k] = g0;
-            }
-        } else {
-            if (act) {
-                const int o = gnode * st.nlen_max + st.nonant_off[k];
-                atomicAdd(&node_buf[o], w * v);
-                atomicAdd(&node_buf[half + o], w * v * v);
-            }
-            if ((threadIdx.x & (WAVE - 1)) == 0) st.part_node[wave * st.nn + k] = -1;
-        }
-    }
-}
-
-// out[0] |= 1 if some wave of local scenarios spans two nodes at a nonant's depth (the
-// test k_xbar_partial makes per wave)
-// out[1] |= 1 if some local scenario's node at a nonant's depth differs from scenario 0's
-__global__ void __launch_bounds__(BLOCK) k_xbar_mixed(phgpu_state st, int32_t* __restrict__ out) {
-    const int64_t S = st.S;
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool act = s < S;
-    bool mixed = false, multi = false;
-    for (int k = 0; k < st.nn; ++k) {
-        const int d = st.nonant_depth[k];
-        const int gnode = act ? st.node_of[IX(d)] : -1;
-        const int g0 = __shfl(gnode, 0, WAVE);
-        mixed |= __any(act && gnode != g0) != 0;
-        multi |= __any(act && gnode != st.node_of[(int64_t)d * S]) != 0;
-    }
-    if (mixed && (threadIdx.x & (WAVE - 1)) == 0) atomicOr(out, 1);
-    if (multi && (threadIdx.x & (WAVE - 1)) == 0) atomicOr(out + 1, 1);
-}
-
-// Ordered segmented sum of the per-wave partials, one block per nonant.  The local
-// scenarios are in tree order, so each node's waves form ONE contiguous run: a run
-// that lies inside one thread's chunk of waves is complete and is flushed directly;
-// the first / last run of every chunk go through shared memory and thread 0 merges
-// them in chunk order (deterministic for every wave-uniform node).
-// x̄ partial of nonant k over chunk w recomputed from x (a chunk of the path-6 epilogue
-// partials with a scenario the fallback solved), in scenario order
-__device__ __forceinline__ void xp_recompute(const phgpu_state& st, const double* __restrict__ x, int64_t w, int C,
-                                             int k, double& a, double& b) {
-    const int64_t S = st.S;
-    const int d = st.nonant_depth[k], j = st.nonant_col[k];
-    const int64_t s1 = (w + 1) * C < S ? (w + 1) * C : S;
-    a = b = 0.0;
-    for (int64_t s = w * C; s < s1; ++s) {
-        const double p = st.pvar ? st.pvar[IX(k)] : st.pcoef[IX(d)], v = x[IX(j)];
-        a += p * v;
-        b += p * v * v;
-    }
-}
-
-#define XF_THREADS 256
-// assign: node_buf was not cleared (one tree node, every entry is some nonant's): the fast
-// path stores its sums instead of adding them (phgpu_ph_reduce: one launch less per step)
-__global__ void __launch_bounds__(XF_THREADS) k_xbar_final(phgpu_state st, double* __restrict__ node_buf,
-                                                           const int32_t* __restrict__ dirty = nullptr,
-                                                           int xpC = 0, const double* __restrict__ x = nullptr,
-                                                           int assign = 0) {
-    __shared__ int fnode[XF_THREADS], lnode[XF_THREADS];
-    __shared__ double fa[XF_THREADS], fb[XF_THREADS], la[XF_THREADS], lb[XF_THREADS];
-    const int k = blockIdx.x;
-    const int t = threadIdx.x;
-    const int half = st.num_nodes * st.nlen_max;
-    const int off = st.nonant_off[k];
-    const int64_t nw = st.nwaves;
-    const int64_t C = (nw + XF_THREADS - 1) / XF_THREADS;
-    const int64_t w0 = (int64_t)t * C, w1 = (w0 + C < nw) ? w0 + C : nw;
-    int cur = -1, first = -1;
-    double a = 0.0, b = 0.0, a_first = 0.0, b_first = 0.0;
-    for (int64_t w = w0; w < w1; ++w) {
-        // the chunk's node, dirty flag and partials in flight together (none gates another
-        // load: one memory round trip per chunk instead of three on the x̄ critical path)
-        const int gnode = st.part_node[w * st.nn + k];
-        const int dw = dirty ? dirty[w] : 0;
-        const double pa = st.part[(w * st.nn + k) * 2 + 0], pb = st.part[(w * st.nn + k) * 2 + 1];
-        if (gnode < 0) continue;
-        if (gnode != cur) {
-            if (cur >= 0) {
-                if (first < 0) {  // close the chunk's first run
-                    first = cur;
-                    a_first = a;
-                    b_first = b;
-                } else {          // a complete middle run
-                    atomicAdd(&node_buf[cur * st.nlen_max + off], a);
-                    atomicAdd(&node_buf[half + cur * st.nlen_max + off], b);
-                }
-            }
-            cur = gnode;
-            a = 0.0;
-            b = 0.0;
-        }
-        if (dw) {
-            double ra, rb;
-            xp_recompute(st, x, w, xpC, k, ra, rb);
-            a += ra;
-            b += rb;
-        } else {
-            a += pa;
-            b += pb;
-        }
-    }
-    if (first < 0) {  // zero or one run in this chunk: it is the first (and last) run
-        fnode[t] = cur;
-        fa[t] = a;
-        fb[t] = b;
-        lnode[t] = -1;
-        la[t] = lb[t] = 0.0;
-    } else {
-        fnode[t] = first;
-        fa[t] = a_first;
-        fb[t] = b_first;
-        lnode[t] = cur;
-        la[t] = a;
-        lb[t] = b;
-    }
-    __syncthreads();
-    // fast path (every two-stage problem, and any nonant whose local scenarios share one
-    // node): all runs belong to thread 0's node -> fixed-order tree sum
-    __shared__ int single;
-    if (t == 0) single = 1;
-    __syncthreads();
-    {
-        const int g0 = fnode[0] >= 0 ? fnode[0] : lnode[0];
-        if ((fnode[t] >= 0 && fnode[t] != g0) || (lnode[t] >= 0 && lnode[t] != g0)) single = 0;
-    }
-    __syncthreads();
-    if (single) {
-        fa[t] += la[t];
-        fb[t] += lb[t];
-        __syncthreads();
-        for (int off = XF_THREADS / 2; off > 0; off >>= 1) {
-            if (t < off) {
-                fa[t] += fa[t + off];
-                fb[t] += fb[t + off];
-            }
-            __syncthreads();
-        }
-        if (t == 0) {
-            int g0 = -1;
-            for (int u = 0; u < XF_THREADS && g0 < 0; ++u) g0 = fnode[u] >= 0 ? fnode[u] : lnode[u];
-            if (g0 >= 0 && assign) {
-                node_buf[g0 * st.nlen_max + off] = fa[0];
-                node_buf[half + g0 * st.nlen_max + off] = fb[0];
-            } else if (g0 >= 0) {
-                node_buf[g0 * st.nlen_max + off] += fa[0];
-                node_buf[half + g0 * st.nlen_max + off] += fb[0];
-            }
-        }
-        return;
-    }
-    // several nodes: every run is flushed once, by the thread where it starts (its owner),
-    // which adds the continuation pieces of the following threads in thread order.  All
-    // runs flush in parallel (a serial merge by one thread cost ~0.2 ms per launch on
-    // 1,057 aircond nodes); one flush per node keeps tree-ordered sums deterministic.
-    // (lnode[u] >= 0 implies fnode[u] >= 0: a chunk's runs are maximal and distinct.)
-    for (int side = 0; side < 2; ++side) {
-        const int g = side ? lnode[t] : fnode[t];
-        if (g < 0) continue;
-        if (side == 0) {  // does the first run continue the previous non-empty chunk's tail?
-            int p = t - 1;
-            while (p >= 0 && fnode[p] < 0) --p;
-            if (p >= 0 && (lnode[p] >= 0 ? lnode[p] : fnode[p]) == g) continue;
-        }
-        double sa = side ? la[t] : fa[t];
-        double sb = side ? lb[t] : fb[t];
-        if (side == 1 || lnode[t] < 0) {  // this run reaches the end of the chunk
-            for (int u = t + 1; u < XF_THREADS; ++u) {
-                if (fnode[u] < 0) continue;  // empty chunk
-                if (fnode[u] != g) break;
-                sa += fa[u];
-                sb += fb[u];
-                if (lnode[u] >= 0) break;    // the run ends inside chunk u
-            }
-        }
-        atomicAdd(&node_buf[g * st.nlen_max + off], sa);
-        atomicAdd(&node_buf[half + g * st.nlen_max + off], sb);
-    }
-}
-
-// ------------------------------------------------------------------ adaptive rho
-// The residual sums of NormRhoUpdater and the two convergers (include/phgpu.h
-// phgpu_ph_residuals) by the scheme of k_xbar_partial / k_xbar_final, with four values per
-// (wave, nonant) in partials of their own (st.rs_part / st.rs_node).
-#define RS_NV 4  // planes: prob |x - x̄|, pcoef |x - x̄|, rho, prob rho
-
-// both outputs of phgpu_ph_residuals to 0 (entries no local scenario reaches stay 0)
-__global__ void __launch_bounds__(256) k_resid_clear(double* __restrict__ planes, int64_t np,
-                                                     double* __restrict__ rho_last, int64_t nl) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < np + nl; i += stride) {
-        if (i < np) planes[i] = 0.0;
-        else rho_last[i - np] = 0.0;
-    }
-}
-
-// norm_rho_updater.py:73-83 (plane 0), primal_dual_converger.py:66-82 and 96-107 (planes 1,
-// 2), norm_rho_converger.py:26 (plane 3): per-wave partial sums, one nonant per grid row; a
-// wave whose scenarios share one node writes one partial (deterministic), a mixed wave adds
-// per lane with fp64 atomics.  rho_last (norm_rho_updater.py:98-104, the last local
-// scenario's rho at each node): the local scenarios are in tree order, so a node's scenarios
-// are one run, and the lane at the end of a run stores its rho.
-__global__ void __launch_bounds__(BLOCK)
-k_resid_partial(phgpu_state st, const double* __restrict__ x, const double* __restrict__ xbar,
-                const double* __restrict__ rho, double* __restrict__ planes, double* __restrict__ rho_last) {
-    const int64_t S = st.S;
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t wave = s / WAVE;
-    const bool act = s < S;
-    const int half = st.num_nodes * st.nlen_max;
-    const int k = blockIdx.y;
-    if (k >= st.nn) return;
-    const int d = st.nonant_depth[k];
-    const int gnode = act ? st.node_of[IX(d)] : -1;
-    const int gnext = (act && s + 1 < S) ? st.node_of[IX(d) + 1] : -1;
-    const double r = act ? rho[IX(k)] : 0.0;
-    const double ad = act ? fabs(x[IX(st.nonant_col[k])] - xbar[IX(k)]) : 0.0;
-    const double pi = act ? st.prob[s] : 0.0;
-    const double pc = act ? (st.pvar ? st.pvar[IX(k)] : st.pcoef[IX(d)]) : 0.0;
-    double v[RS_NV] = {pi * ad, pc * ad, r, pi * r};
-    if (act && gnext != gnode) rho_last[gnode * st.nlen_max + st.nonant_off[k]] = r;
-    const int g0 = __shfl(gnode, 0, WAVE);
-    const bool uniform = !__any(act && gnode != g0);
-    if (uniform) {
-#pragma unroll
-        for (int j = 0; j < RS_NV; ++j) v[j] = wave_sum(v[j]);
-        if ((threadIdx.x & (WAVE - 1)) == 0) {
-#pragma unroll
-            for (int j = 0; j < RS_NV; ++j) st.rs_part[(wave * st.nn + k) * RS_NV + j] = v[j];
-            st.rs_node[wave * st.nn + k] = g0;
-        }
-    } else {
-        if (act) {
-            const int o = gnode * st.nlen_max + st.nonant_off[k];
-#pragma unroll
-            for (int j = 0; j < RS_NV; ++j) atomicAdd(&planes[(int64_t)j * half + o], v[j]);
-        }
-        if ((threadIdx.x & (WAVE - 1)) == 0) st.rs_node[wave * st.nn + k] = -1;
-    }
-}
-
-// k_xbar_final for the four residual values: ordered segmented sum of the per-wave partials,
-// one block per nonant, into the cleared planes.  A run (one node's consecutive waves) inside
-// one thread's chunk is flushed by that thread; a run that crosses chunks is flushed once, by
-// the thread where it starts, which adds the following chunks' pieces in thread order; a
-// nonant whose waves all share one node takes the fixed-order tree sum.
-// assign: the planes were not cleared (one tree node, every entry is some nonant's): the
-// fixed-order sum is stored, not added (as k_xbar_final's assign).
-// MAXMASK: bit j set = plane j is a maximum, not a sum (phgpu_nonant_stats' planes 2 and 3;
-// cleared to -inf); part / node: the caller's per-wave partials and node tags; NV: the number
-// of planes (and of values per (wave, nonant) in part), RS_NV unless stated.
-template <int MAXMASK>
-__device__ __forceinline__ double pl_id(int j) {
-    return ((MAXMASK >> j) & 1) ? -INFINITY : 0.0;
-}
-template <int MAXMASK>
-__device__ __forceinline__ double pl_op(int j, double a, double b) {
-    return ((MAXMASK >> j) & 1) ? fmax(a, b) : a + b;
-}
-template <int MAXMASK>
-__device__ __forceinline__ void pl_atomic(int j, double* p, double v) {
-    if ((MAXMASK >> j) & 1) atomicMax(p, v);
-    else atomicAdd(p, v);
-}
-
-template <int MAXMASK, int NV = RS_NV>
-__global__ void __launch_bounds__(XF_THREADS)
-k_resid_final(phgpu_state st, const double* __restrict__ part, const int32_t* __restrict__ node,
-              double* __restrict__ planes, int assign) {
-    __shared__ int fnode[XF_THREADS], lnode[XF_THREADS];
-    __shared__ double fv[NV][XF_THREADS], lv[NV][XF_THREADS];
-    __shared__ int single;
-    const int k = blockIdx.x;
-    const int t = threadIdx.x;
-    const int64_t half = (int64_t)st.num_nodes * st.nlen_max;
-    const int off = st.nonant_off[k];
-    const int64_t nw = st.nwaves;
-    const int64_t C = (nw + XF_THREADS - 1) / XF_THREADS;
-    const int64_t w0 = (int64_t)t * C, w1 = (w0 + C < nw) ? w0 + C : nw;
-    int cur = -1, first = -1;
-    double a[NV], a_first[NV];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) a[j] = a_first[j] = pl_id<MAXMASK>(j);
-    for (int64_t w = w0; w < w1; ++w) {
-        const int gnode = node[w * st.nn + k];
-        double p[NV];
-#pragma unroll
-        for (int j = 0; j < NV; ++j) p[j] = part[(w * st.nn + k) * NV + j];
-        if (gnode < 0) continue;
-        if (gnode != cur) {
-            if (cur >= 0) {
-                if (first < 0) {  // close the chunk's first run
-                    first = cur;
-#pragma unroll
-                    for (int j = 0; j < NV; ++j) a_first[j] = a[j];
-                } else {          // a complete middle run
-#pragma unroll
-                    for (int j = 0; j < NV; ++j) pl_atomic<MAXMASK>(j, &planes[j * half + cur * st.nlen_max + off], a[j]);
-                }
-            }
-            cur = gnode;
-#pragma unroll
-            for (int j = 0; j < NV; ++j) a[j] = pl_id<MAXMASK>(j);
-        }
-#pragma unroll
-        for (int j = 0; j < NV; ++j) a[j] = pl_op<MAXMASK>(j, a[j], p[j]);
-    }
-    if (t == 0) single = 1;
-    if (first < 0) {  // zero or one run in this chunk: it is the first (and last) run
-        fnode[t] = cur;
-        lnode[t] = -1;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            fv[j][t] = a[j];
-            lv[j][t] = pl_id<MAXMASK>(j);
-        }
-    } else {
-        fnode[t] = first;
-        lnode[t] = cur;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            fv[j][t] = a_first[j];
-            lv[j][t] = a[j];
-        }
-    }
-    __syncthreads();
-    {
-        const int g0 = fnode[0] >= 0 ? fnode[0] : lnode[0];
-        if ((fnode[t] >= 0 && fnode[t] != g0) || (lnode[t] >= 0 && lnode[t] != g0)) single = 0;
-    }
-    __syncthreads();
-    if (single) {
-#pragma unroll
-        for (int j = 0; j < NV; ++j) fv[j][t] = pl_op<MAXMASK>(j, fv[j][t], lv[j][t]);
-        __syncthreads();
-        for (int o = XF_THREADS / 2; o > 0; o >>= 1) {
-            if (t < o) {
-#pragma unroll
-                for (int j = 0; j < NV; ++j) fv[j][t] = pl_op<MAXMASK>(j, fv[j][t], fv[j][t + o]);
-            }
-            __syncthreads();
-        }
-        if (t == 0) {
-            int g0 = -1;
-            for (int u = 0; u < XF_THREADS && g0 < 0; ++u) g0 = fnode[u] >= 0 ? fnode[u] : lnode[u];
-            if (g0 >= 0) {
-#pragma unroll
-                for (int j = 0; j < NV; ++j) {
-                    double* q = &planes[j * half + g0 * st.nlen_max + off];
-                    *q = assign ? fv[j][0] : pl_op<MAXMASK>(j, *q, fv[j][0]);
-                }
-            }
-        }
-        return;
-    }
-    // (lnode[u] >= 0 implies fnode[u] >= 0: a chunk's runs are maximal and distinct.)
-    for (int side = 0; side < 2; ++side) {
-        const int g = side ? lnode[t] : fnode[t];
-        if (g < 0) continue;
-        if (side == 0) {  // does the first run continue the previous non-empty chunk's tail?
-            int p = t - 1;
-            while (p >= 0 && fnode[p] < 0) --p;
-            if (p >= 0 && (lnode[p] >= 0 ? lnode[p] : fnode[p]) == g) continue;
-        }
-        double sv[NV];
-#pragma unroll
-        for (int j = 0; j < NV; ++j) sv[j] = side ? lv[j][t] : fv[j][t];
-        if (side == 1 || lnode[t] < 0) {  // this run reaches the end of the chunk
-            for (int u = t + 1; u < XF_THREADS; ++u) {
-                if (fnode[u] < 0) continue;  // empty chunk
-                if (fnode[u] != g) break;
-#pragma unroll
-                for (int j = 0; j < NV; ++j) sv[j] = pl_op<MAXMASK>(j, sv[j], fv[j][u]);
-                if (lnode[u] >= 0) break;    // the run ends inside chunk u
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < NV; ++j) pl_atomic<MAXMASK>(j, &planes[j * half + g * st.nlen_max + off], sv[j]);
-    }
-}
-
-// NormRhoUpdater.miditer's rule (norm_rho_updater.py:128-143) for every local (k, s): one
-// nonant per grid row, a row's blocks stride over the scenarios (the grid of k_ph_update).
-// The residuals are per (node, nonant), so every rank and every scenario of a node takes the
-// same branch.  counts (may be null): entries that took no action / increase / decrease /
-// converged decrease, by integer atomics (one per wave and action).
-#define NR_T 256
-#define NR_U 4
-__global__ void __launch_bounds__(NR_T)
-k_norm_rho_update(phgpu_state st, phgpu_norm_rho_params prm, const double* __restrict__ plane0,
-                  const double* __restrict__ rho_last, const double* __restrict__ xbar_node,
-                  const double* __restrict__ xbar_prev, double* __restrict__ rho,
-                  unsigned long long* __restrict__ counts) {
-    const int64_t S = st.S;
-    const int k = blockIdx.y;
-    int c[4] = {0, 0, 0, 0};
-    if (k < st.nn) {
-        const int d = st.nonant_depth[k];
-        const int off = st.nonant_off[k], nl = st.nlen_max;
-        const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-        for (int64_t s0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s0 < S; s0 += NR_U * stride) {
-            double p[NR_U], dr[NR_U], r[NR_U];
-#pragma unroll
-            for (int u = 0; u < NR_U; ++u) {
-                const int64_t s = s0 + u * stride;
-                p[u] = dr[u] = r[u] = 0.0;
-                if (s < S) {
-                    const int o = st.node_of[(int64_t)d * S + s] * nl + off;
-                    p[u] = plane0[o];
-                    dr[u] = rho_last[o] * fabs(xbar_node[o] - xbar_prev[o]);
-                    r[u] = rho[(int64_t)k * S + s];
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < NR_U; ++u) {
-                const int64_t s = s0 + u * stride;
-                if (s < S) {
-                    int act = 0;
-                    if (p[u] > prm.f * dr[u] && p[u] > prm.tol) {
-                        act = 1;
-                        rho[(int64_t)k * S + s] = r[u] * prm.inc;
-                    } else if (dr[u] > prm.f * p[u] && dr[u] > prm.tol) {
-                        if (prm.allow_decrease) {
-                            act = 2;
-                            rho[(int64_t)k * S + s] = r[u] / prm.dec;
-                        }
-                    } else if (p[u] < prm.tol && dr[u] < prm.tol) {
-                        act = 3;
-                        rho[(int64_t)k * S + s] = r[u] / prm.conv_dec;
-                    }
-#pragma unroll
-                    for (int a = 0; a < 4; ++a) c[a] += act == a;
-                }
-            }
-        }
-    }
-    if (counts) {
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            int v = c[a];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, WAVE);
-            if ((threadIdx.x & (WAVE - 1)) == 0 && v) atomicAdd(&counts[a], (unsigned long long)v);
-        }
-    }
-}
-
-// ------------------------------------------------------------------ xhat candidates
-// Per-node statistics of a nonant array v[nn*S] (k-major, like W or a spoke's localnonants):
-// the candidates of XhatXbar (extensions/xhatxbar.py:38-55: the node's x̄), the slam
-// heuristics (cylinders/slam_heuristic.py:57-67, 84: the column-wise max / min) and the x̄ /
-// x̄² XhatClosest measures against (extensions/xhatclosest.py:37-45), by the scheme of
-// k_resid_partial / k_resid_final: planes 0-1 are sums, planes 2-3 maxima (the minimum is
-// stored negated, so that one MAX over the ranks serves both).
-#define NS_KU 4  // nonants per grid row: their loads are in flight together
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, WAVE));
-    return v;
-}
-
-// planes 0-1 to 0, planes 2-3 to -inf (what an entry no local scenario reaches keeps)
-__global__ void __launch_bounds__(256) k_nstats_clear(double* __restrict__ planes, int64_t half) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < RS_NV * half; i += stride)
-        planes[i] = i < 2 * half ? 0.0 : -INFINITY;
-}
-
-// One lane per scenario, NS_KU nonants per grid row.  A wave whose scenarios share one node
-// writes one partial per plane (deterministic); a mixed wave goes to the planes per lane by
-// fp64 atomics (add / max).
-__global__ void __launch_bounds__(BLOCK)
-k_nstats_partial(phgpu_state st, const double* __restrict__ v, double* __restrict__ planes) {
-    const int64_t S = st.S;
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t wave = s / WAVE;
-    const bool act = s < S;
-    const int64_t half = (int64_t)st.num_nodes * st.nlen_max;
-    const int k0 = blockIdx.y * NS_KU;
-    double val[NS_KU], pc[NS_KU];
-    int gn[NS_KU];
-#pragma unroll
-    for (int u = 0; u < NS_KU; ++u) {
-        const int k = k0 + u;
-        const bool on = act && k < st.nn;
-        const int d = k < st.nn ? st.nonant_depth[k] : 0;
-        gn[u] = on ? st.node_of[IX(d)] : -1;
-        val[u] = on ? v[IX(k)] : 0.0;
-        pc[u] = on ? (st.pvar ? st.pvar[IX(k)] : st.pcoef[IX(d)]) : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < NS_KU; ++u) {
-        const int k = k0 + u;
-        if (k >= st.nn) break;
-        const int gnode = gn[u];
-        double w[RS_NV] = {pc[u] * val[u], pc[u] * val[u] * val[u], act ? -val[u] : -INFINITY,
-                           act ? val[u] : -INFINITY};
-        const int g0 = __shfl(gnode, 0, WAVE);
-        const bool uniform = !__any(act && gnode != g0);
-        if (uniform) {
-            w[0] = wave_sum(w[0]);
-            w[1] = wave_sum(w[1]);
-            w[2] = wave_max(w[2]);
-            w[3] = wave_max(w[3]);
-            if ((threadIdx.x & (WAVE - 1)) == 0) {
-#pragma unroll
-                for (int j = 0; j < RS_NV; ++j) st.ns_part[(wave * st.nn + k) * RS_NV + j] = w[j];
-                st.ns_node[wave * st.nn + k] = g0;
-            }
-        } else {
-            if (act) {
-                const int64_t o = (int64_t)gnode * st.nlen_max + st.nonant_off[k];
-                atomicAdd(&planes[o], w[0]);
-                atomicAdd(&planes[half + o], w[1]);
-                atomicMax(&planes[2 * half + o], w[2]);
-                atomicMax(&planes[3 * half + o], w[3]);
-            }
-            if ((threadIdx.x & (WAVE - 1)) == 0) st.ns_node[wave * st.nn + k] = -1;
-        }
-    }
-}
-
-// xhatclosest.py:37-51 for a two-stage handle: one lane per scenario sums, k ascending, the
-// truncated z-scores min(3, |v - x̄| / sqrt(var)) of the nonants with var = x̄² - x̄ x̄ > 0
-// (strict), NC_KU loads of v in flight.  The smallest distance and the lowest local index
-// attaining it (the reference's strict < scan): (distance, index) pairs reduced per wave and
-// per block, the block's pair swapped into bpart, and the block with the last ticket reduces
-// the pairs and stores best (conv_last_block's exchange / ticket chain: agent-scope atomic
-// read-modify-writes, no fence).  The lexicographic minimum does not depend on the order.
-// The index travels as a double (exact below 2^53), as best[1] returns it.
-#define NC_T 256
-#define NC_KU 4
-__device__ __forceinline__ void argmin_take(double& d, double& i, double od, double oi) {
-    if (od < d || (od == d && oi < i)) {
-        d = od;
-        i = oi;
-    }
-}
-
-__global__ void __launch_bounds__(NC_T)
-k_nonant_closest(phgpu_state st, const double* __restrict__ v, const double* __restrict__ xbar_node,
-                 const double* __restrict__ xsqbar_node, double* __restrict__ dist, double* __restrict__ bpart,
-                 int32_t* __restrict__ cnt, double* __restrict__ best) {
-    __shared__ double rd[NC_T / WAVE], ri[NC_T / WAVE];
-    __shared__ int last;
-    const int64_t S = st.S;
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool act = s < S;
-    const int nn = st.nn;
-    double acc = 0.0;
-    for (int k0 = 0; k0 < nn; k0 += NC_KU) {
-        double val[NC_KU];
-#pragma unroll
-        for (int u = 0; u < NC_KU; ++u) val[u] = (act && k0 + u < nn) ? v[IX(k0 + u)] : 0.0;
-#pragma unroll
-        for (int u = 0; u < NC_KU; ++u) {
-            if (k0 + u >= nn) break;
-            const int o = st.nonant_off[k0 + u];
-            const double xb = xbar_node[o];
-            const double var = xsqbar_node[o] - xb * xb;
-            if (var > 0.0) acc += fmin(3.0, fabs(val[u] - xb) / sqrt(var));
-        }
-    }
-    if (act && dist) dist[s] = acc;
-    double d = act ? acc : INFINITY, i = act ? (double)s : INFINITY;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        argmin_take(d, i, __shfl_down(d, off, WAVE), __shfl_down(i, off, WAVE));
-    const int wv = threadIdx.x / WAVE;
-    if ((threadIdx.x & (WAVE - 1)) == 0) {
-        rd[wv] = d;
-        ri[wv] = i;
-    }
-    __syncthreads();
-    const int nblk = (int)gridDim.x;
-    if (threadIdx.x == 0) {
-        for (int u = 1; u < NC_T / WAVE; ++u) argmin_take(d, i, rd[u], ri[u]);
-        const double o0 = __hip_atomic_exchange(&bpart[2 * blockIdx.x], d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const double o1 =
-            __hip_atomic_exchange(&bpart[2 * blockIdx.x + 1], i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // both swaps have returned before the ticket is taken (see conv_last_block)
-        asm volatile("" ::"v"(o0), "v"(o1) : "memory");
-        const int tk = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = tk == nblk - 1;
-    }
-    __syncthreads();
-    if (!last) return;
-    d = INFINITY;
-    i = INFINITY;
-    for (int b = threadIdx.x; b < nblk; b += blockDim.x) {
-        const double od = __hip_atomic_fetch_add(&bpart[2 * b], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const double oi = __hip_atomic_fetch_add(&bpart[2 * b + 1], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        argmin_take(d, i, od, oi);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        argmin_take(d, i, __shfl_down(d, off, WAVE), __shfl_down(i, off, WAVE));
-    __syncthreads();
-    if ((threadIdx.x & (WAVE - 1)) == 0) {
-        rd[wv] = d;
-        ri[wv] = i;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int u = 1; u < NC_T / WAVE; ++u) argmin_take(d, i, rd[u], ri[u]);
-        best[1] = i;
-        best[0] = d;
-        __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-// ------------------------------------------------------------------ gradient rho
-// The cost-proportional rho of mpisppy/utils/gradient.py, find_rho.py and
-// extensions/gradient_extension.py with the dual metric of utils/wtracker.py:134-157
-// (include/phgpu.h phgpu_grad_cost .. phgpu_rho_from_stats): four single passes over at most
-// nn * S doubles.
-#define GR_T 256
-#define GR_ROWS 65535  // grid rows at most (gridDim.y's limit): a kernel with a nonant per row strides over them
-
-// c and q of column j of scenario s in original units: the library's copies, or on a
-// shared-matrix handle words 0 and 1 of the column's per-scenario record (k_sh_fill; every
-// nonant column has one)
-__device__ __forceinline__ void obj_cq(const phgpu_state& st, int j, int64_t s, double& c, double& q) {
-    if (st.shared) {
-        const double* e = st.sk + (size_t)s * (size_t)st.sk_stride + st.sk_PC + 8 * (size_t)st.cmap[j];
-        c = e[0];
-        q = e[1];
-    } else {
-        c = st.c[(size_t)j * (size_t)st.S + (size_t)s];
-        q = st.q[(size_t)j * (size_t)st.S + (size_t)s];
-    }
-}
-
-// gradient.py:65-81 for f(x) = c.x + 1/2 x.diag(q).x: cost[k, s] = -(c + q xn[k, s]), one
-// nonant per grid row
-__global__ void __launch_bounds__(GR_T)
-k_grad_cost(phgpu_state st, const double* __restrict__ xn, double* __restrict__ cost) {
-    const int64_t S = st.S;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int k = blockIdx.y; k < st.nn; k += gridDim.y) {  // (more nonants than grid rows: strided)
-        const int j = st.nonant_col[k];
-        for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < S; s += stride) {
-#pragma clang fp contract(off)  // two roundings, as numpy's c + q * x: no fused multiply-add
-            double c, q;
-            obj_cq(st, j, s, c, q);
-            const double qx = q * xn[IX(k)];
-            cost[IX(k)] = -(c + qx);
-        }
-    }
-}
-
-// A block's threads summed in a fixed order (wave shuffles, then the waves' sums in wave
-// order); the result is thread 0's
-__device__ __forceinline__ double block_sum_fixed(double v, double* red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & (WAVE - 1)) == 0) red[threadIdx.x / WAVE] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0)
-        for (int u = 0; u < (int)(blockDim.x / WAVE); ++u) t += red[u];
-    return t;
-}
-
-// wtracker.py:141-154: out[0] = scale x sum over the local (k, s) of |W - W_prev|, and W_prev
-// = W in the same pass.  Every thread adds its elements in index order, every block its threads
-// in a fixed order; the block's sum is swapped into bpart and the block with the last ticket
-// adds the blocks' sums in block order and stores out (k_nonant_closest's exchange / ticket
-// chain): the same bits on every run.  The grid has at most WD_BLOCKS blocks.
-#define WD_BLOCKS 256
-__global__ void __launch_bounds__(GR_T)
-k_w_diff(const double* __restrict__ W, double* __restrict__ W_prev, int64_t tot, double scale,
-         double* __restrict__ bpart, int32_t* __restrict__ cnt, double* __restrict__ out) {
-    __shared__ double red[GR_T / WAVE];
-    __shared__ double fin[WD_BLOCKS];
-    __shared__ int last;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    double acc = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += stride) {
-        const double w = W[i];
-        acc += fabs(w - W_prev[i]);
-        W_prev[i] = w;
-    }
-    const double b = block_sum_fixed(acc, red);
-    const int nblk = (int)gridDim.x;
-    if (threadIdx.x == 0) {
-        const double o0 = __hip_atomic_exchange(&bpart[blockIdx.x], b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // the swap has returned before the ticket is taken (see conv_last_block)
-        asm volatile("" ::"v"(o0) : "memory");
-        const int tk = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = tk == nblk - 1;
-    }
-    __syncthreads();
-    if (!last) return;
-    for (int u = threadIdx.x; u < WD_BLOCKS; u += blockDim.x)
-        fin[u] = u < nblk ? __hip_atomic_fetch_add(&bpart[u], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
-    __syncthreads();
-    for (int o = WD_BLOCKS / 2; o > 0; o >>= 1) {
-        for (int u = threadIdx.x; u < o; u += blockDim.x) fin[u] += fin[u + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        out[0] = scale * fin[0];
-        __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-// find_rho.py:170-203 up to the order statistic, for a two-stage handle: r[k, s] = |cost[k, s]|
-// / denominator and, per nonant, the per-wave partials of sum r, max(-r) and max(r) for
-// k_resid_final<0x6, 3> (every wave's scenarios share the one node).  One lane per scenario.
-//   gden == null: the scenario's own denominator, the largest over its nonants j of
-//     max(|x_j - x̄_j|, 2 (x_j - x̄_j)^2): np.max((w_denom, prox_denom)) at find_rho.py:189
-//     is ONE scalar per scenario (:78-115);
-//   gden given:   gden[offset of k] for every scenario (_grad_denom, :118-147).
-// IEEE division (numpy's): a zero denominator gives +inf (0 / 0 NaN, which fmax drops).
-#define RR_NV 3  // planes: sum r, max(-r), max(r)
-__global__ void __launch_bounds__(BLOCK)
-k_rho_ratio_partial(phgpu_state st, const double* __restrict__ cost, const double* __restrict__ x,
-                    const double* __restrict__ xbar, const double* __restrict__ gden) {
-    const int64_t S = st.S;
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t wave = s / WAVE;
-    const bool act = s < S;
-    const int nn = st.nn;
-    double d = 0.0;
-    if (!gden && act) {
-        for (int k = 0; k < nn; ++k) {
-            const double dx = x[IX(st.nonant_col[k])] - xbar[IX(k)];
-            d = fmax(d, fmax(fabs(dx), 2.0 * (dx * dx)));
-        }
-    }
-    const int g0 = __shfl(act ? st.node_of[s] : 0, 0, WAVE);
-    for (int k = 0; k < nn; ++k) {
-        double r = 0.0;
-        if (act) r = fabs(cost[IX(k)]) / (gden ? gden[st.nonant_off[k]] : d);
-        const double sum = wave_sum(r);
-        const double mn = wave_max(act ? -r : -INFINITY);
-        const double mx = wave_max(act ? r : -INFINITY);
-        if ((threadIdx.x & (WAVE - 1)) == 0) {
-            double* p = &st.rr_part[(wave * nn + k) * RR_NV];
-            p[0] = sum;
-            p[1] = mn;
-            p[2] = mx;
-            st.rr_node[wave * nn + k] = g0;
-        }
-    }
-}
-
-// the planes of phgpu_rho_ratio_stats an entry without a nonant keeps: 0, -inf, -inf
-__global__ void __launch_bounds__(256) k_rr_clear(double* __restrict__ planes, int64_t half) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < RR_NV * half; i += stride)
-        planes[i] = i < half ? 0.0 : -INFINITY;
-}
-
-// find_rho.py:150-168 (_order_stat) and the rho rewrite of gradient_extension.py:85-94 for a
-// two-stage handle: every local rho[k, s] becomes the order statistic of nonant k's ratios,
-// if the gate is open -- |(prev - cur) / prev| <= thr on gate = {prev, cur}, which NaN and
-// inf fail (gradient_extension.py:65-68); a null gate is open.  Every thread evaluates the
-// gate itself (two cached loads); a closed gate stores nothing to rho.  One nonant per grid
-// row; applied (may be null) is stored by the grid's first thread.
-__global__ void __launch_bounds__(GR_T)
-k_rho_from_stats(phgpu_state st, const double* __restrict__ planes, double s_total, double alpha,
-                 const double* __restrict__ gate, double thr, double* __restrict__ rho,
-                 int32_t* __restrict__ applied) {
-    const int64_t S = st.S;
-    bool open = true;
-    if (gate) {
-        const double prev = gate[0], cur = gate[1];
-        open = fabs((prev - cur) / prev) <= thr;
-    }
-    if (applied && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *applied = open ? 1 : 0;
-    if (!open) return;
-    const int64_t half = (int64_t)st.num_nodes * st.nlen_max;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int k = blockIdx.y; k < st.nn; k += gridDim.y) {  // (more nonants than grid rows: strided)
-        const int off = st.nonant_off[k];
-        const double mean = planes[off] / s_total;
-        const double mn = -planes[half + off], mx = planes[2 * half + off];
-        double v;
-        if (alpha == 0.5) v = mean;
-        else if (alpha < 0.5) v = mn + alpha * 2.0 * (mean - mn);
-        else v = (2.0 * mean - mx) + alpha * 2.0 * (mx - mean);
-        for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < S; s += stride) rho[IX(k)] = v;
-    }
-}
-
-// Where the update kernels leave conv (phbase.py:330-339) and the last solve's statistics
-struct conv_sink {
-    double* conv;                          // conv_local (pinned host or device memory)
-    const unsigned long long* stats_src;   // the last solve's statistics (device), or null
-    int stats_copies;                      // copies of them at stats_src (stats_word)
-    int64_t* stats_dst;                    // where they go (pinned host or device), or null
-    double scale;                          // 1 / (S nn)
-    double* cpart;                         // [gridDim.x] block partials
-    int32_t* cnt;                          // last-block counter (0 between launches)
-};
-
-// conv = scale x (sum over the grid of every thread's acc), without a second launch: each
-// block reduces its threads in a fixed order and swaps its partial into cpart[block], then
-// takes a ticket; the block with the last ticket sums cpart in block order (deterministic)
-// and stores the statistics, then conv.  Every cross-block exchange is an agent-scope atomic
-// read-modify-write, performed at the device's coherence point, so no block needs a release
-// fence (an L2 writeback on gfx950); the ticket is taken only after the swap
-// has returned.  The host reads stats after it sees conv (phgpu_ph_update_ex).
-__device__ __forceinline__ void conv_last_block(double acc, const conv_sink& o) {
-    __shared__ double red[XL_T / WAVE];
-    __shared__ int last;
-    const int wv = threadIdx.x / WAVE, nwb = (int)(blockDim.x / WAVE);
-    // the solve's statistics copies, loaded now by every block's first wave (the previous
-    // launch wrote them: stream order) and reduced only by the last block -- their load is
-    // off the exchange / ticket chain
-    unsigned long long sv[6];
-    {
-        const int t = threadIdx.x;
-#pragma unroll
-        for (int k = 0; k < 6; ++k)
-            sv[k] = (o.stats_dst && t < o.stats_copies) ? o.stats_src[t * PHGPU_STATS_STRIDE + k] : 0ull;
-    }
-    const int nblk = (int)(gridDim.x * gridDim.y), bid = (int)(blockIdx.y * gridDim.x + blockIdx.x);
-    acc = wave_sum(acc);
-    if ((threadIdx.x & (WAVE - 1)) == 0) red[wv] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int u = 0; u < nwb; ++u) t += red[u];
-        const double old = __hip_atomic_exchange(&o.cpart[bid], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // The swap has returned before the ticket is taken (the empty asm consumes its result,
-        // so the compiler waits for it).  Ordering rests on the hardware, not on the HIP memory
-        // model (both RMWs are relaxed): a returning agent-scope atomic has been performed at
-        // the device's coherence point when its value is back, so the last block's reads of
-        // cpart (agent-scope RMWs as well) see every partial whose ticket precedes its own.
-        // Release / acquire would make it formal at the price of an L2 writeback on every XCD
-        // (15-29 us per launch).  tests/test_gpu_readback.py compares this conv
-        // bit for bit with the ordered device reduction and would catch a reordering.
-        asm volatile("" ::"v"(old) : "memory");
-        const int tk = __hip_atomic_fetch_add(o.cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = tk == nblk - 1;
-    }
-    __syncthreads();
-    if (!last) return;
-    double a = 0.0;
-    for (int b = threadIdx.x; b < nblk; b += blockDim.x)
-        a += __hip_atomic_fetch_add(&o.cpart[b], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    a = wave_sum(a);
-    __syncthreads();
-    if ((threadIdx.x & (WAVE - 1)) == 0) red[wv] = a;
-    __syncthreads();
-    // lanes 0..5 store the statistics and lane 6 conv in one store instruction (no wait for
-    // the host-memory acknowledgements: the host polls conv and the statistics' sentinels,
-    // engine.convergence_wait)
-    if (threadIdx.x < WAVE) {
-        double t = 0.0;
-        for (int u = 0; u < nwb; ++u) t += red[u];
-        if (o.stats_dst) {
-            unsigned long long v[6];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) v[k] = sv[k];
-#pragma unroll
-            for (int o2 = 32; o2 > 0; o2 >>= 1)
-#pragma unroll
-                for (int k = 0; k < 6; ++k) {
-                    const unsigned long long u = __shfl_xor(v[k], o2, 64);
-                    v[k] = k == 5 ? (u > v[k] ? u : v[k]) : v[k] + u;
-                }
-            unsigned long long w = v[0];
-#pragma unroll
-            for (int k = 1; k < 6; ++k) w = (int)threadIdx.x == k ? v[k] : w;
-            if (threadIdx.x < 6) o.stats_dst[threadIdx.x] = (int64_t)w;
-        }
-        if (threadIdx.x == 6) *o.conv = t * o.scale;
-        if (threadIdx.x == 0) __hip_atomic_store(o.cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-// phbase.py:90-103 (scatter x̄), 293-318 (W update), 330-339 (local |x - x̄| sum, reduced
-// by the last block into conv_local).
-#define UPD_T 256
-#define UPD_BLOCKS 256  // at most about this many blocks: each takes a ticket on one counter
-#define UPD_U 4         // scenarios per thread in flight per trip
-__global__ void __launch_bounds__(UPD_T)
-k_ph_update(phgpu_state st, const double* __restrict__ x, const double* __restrict__ node_buf,
-            double* __restrict__ xbar, double* __restrict__ W, const double* __restrict__ rho,
-            int update_W, conv_sink o) {
-    // one nonant per grid row (blockIdx.y): the per-nonant index loads of a scenario's
-    // thread run in parallel instead of one dependent chain per nonant (config 2, 30
-    // nonants: 27 us -> a few).  A row's blocks stride over the scenarios (UPD_U loads in
-    // flight per thread), so that the grid stays near UPD_BLOCKS blocks: the last-block
-    // ticket is one atomic counter, and config 4's 1,536 blocks (65,536 scenarios x 6
-    // nonants) queued on it for about 20 us of a 27 us launch
-    const int64_t S = st.S;
-    const int k = blockIdx.y;
-    double acc = 0.0;
-    if (k < st.nn) {
-        const int d = st.nonant_depth[k];
-        const int off = st.nonant_off[k], col = st.nonant_col[k], nl = st.nlen_max;
-        const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-        for (int64_t s0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s0 < S; s0 += UPD_U * stride) {
-            double xb[UPD_U], xv[UPD_U], wo[UPD_U], rv[UPD_U];
-            bool pz[UPD_U];
-#pragma unroll
-            for (int u = 0; u < UPD_U; ++u) {
-                const int64_t s = s0 + u * stride;
-                xb[u] = xv[u] = wo[u] = rv[u] = 0.0;
-                pz[u] = false;
-                if (s < S) {  // (a wave past S skips its loads: a small batch has one trip of one)
-                    const int gnode = st.node_of[(int64_t)d * S + s];
-                    xb[u] = node_buf[gnode * nl + off];
-                    xv[u] = x[(int64_t)col * S + s];
-                    wo[u] = update_W ? W[(int64_t)k * S + s] : 0.0;
-                    rv[u] = update_W ? rho[(int64_t)k * S + s] : 0.0;
-                    // (variable probabilities: W masked where the probability is 0, phbase.py:315-318)
-                    pz[u] = update_W && st.pvar && st.pvar[(int64_t)k * S + s] == 0.0;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < UPD_U; ++u) {
-                const int64_t s = s0 + u * stride;
-                if (s < S) {
-                    xbar[(int64_t)k * S + s] = xb[u];
-                    if (update_W) W[(int64_t)k * S + s] = pz[u] ? 0.0 : wo[u] + rv[u] * (xv[u] - xb[u]);
-                    acc += fabs(xv[u] - xb[u]);
-                }
-            }
-        }
-    }
-    conv_last_block(acc, o);
-}
-
-// phgpu_ph_step_local (one rank, every nonant's scenarios on one node, nn <= XL_NN_MAX):
-// k_xbar_final and k_ph_update in one launch.  Every block sums the per-wave x̄ partials
-// itself, in one fixed order (so every block gets the same bits), block 0 stores them in
-// node_buf; then the scatter / W update / conv of k_ph_update (last-block reduction).  The
-// partials are per wave (k_xbar_partial) or per chunk of the path-6 epilogue (st.part /
-// st.nwaves then point at those; dirty chunks are recomputed from x).  Few, large blocks for
-// a large batch (every block re-sums the partials), 256 threads for a small one.
-__global__ void __launch_bounds__(XL_T)
-k_ph_update_local(phgpu_state st, const double* __restrict__ x, double* __restrict__ node_buf,
-                  double* __restrict__ xbar, double* __restrict__ W, const double* __restrict__ rho,
-                  int update_W, conv_sink o, const int32_t* __restrict__ dirty, int C) {
-    __shared__ double sa[XL_T / WAVE][XL_NN_MAX], sb[XL_T / WAVE][XL_NN_MAX];
-    __shared__ double xbs[XL_NN_MAX];
-    const int64_t S = st.S;
-    const int nn = st.nn;
-    const int half = st.num_nodes * st.nlen_max;
-    // every nonant at once: strided loads of the contiguous per-wave partials, wave sums,
-    // then the block's waves in order (one barrier)
-    // the scenario's own operands of the first XL_PF nonants, loaded ahead of the x̄ sums
-    // (independent of them; the barrier below would keep them behind)
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t sc = s < S ? s : S - 1;
-    double xv[XL_PF], wo[XL_PF], rv[XL_PF];
-#pragma unroll
-    for (int k = 0; k < XL_PF; ++k) {
-        const int kk = k < nn ? k : 0;
-        xv[k] = x[(int64_t)st.nonant_col[kk] * S + sc];
-        wo[k] = update_W ? W[(int64_t)kk * S + sc] : 0.0;
-        rv[k] = update_W ? rho[(int64_t)kk * S + sc] : 0.0;
-    }
-    double a[XL_NN_MAX], b[XL_NN_MAX];
-#pragma unroll
-    for (int k = 0; k < XL_NN_MAX; ++k) a[k] = b[k] = 0.0;
-    for (int64_t w = threadIdx.x; w < st.nwaves; w += blockDim.x) {
-        const double* pw = st.part + w * nn * 2;
-        // the chunk's flag and partials in flight together (the flag gates the use only)
-        const int dw = dirty ? dirty[w] : 0;
-        double pa[XL_PF], pb[XL_PF];
-#pragma unroll
-        for (int k = 0; k < XL_PF; ++k) {
-            pa[k] = k < nn ? pw[2 * k] : 0.0;
-            pb[k] = k < nn ? pw[2 * k + 1] : 0.0;
-        }
-        if (dw) {  // a chunk with a fallback scenario (path-6 partials)
-            for (int k = 0; k < nn; ++k) {
-                double ra, rb;
-                xp_recompute(st, x, w, C, k, ra, rb);
-#pragma unroll
-                for (int u = 0; u < XL_NN_MAX; ++u)
-                    if (u == k) a[u] += ra, b[u] += rb;
-            }
-            continue;
-        }
-#pragma unroll
-        for (int k = 0; k < XL_NN_MAX; ++k)
-            if (k < nn) {
-                a[k] += k < XL_PF ? pa[k < XL_PF ? k : 0] : pw[2 * k];
-                b[k] += k < XL_PF ? pb[k < XL_PF ? k : 0] : pw[2 * k + 1];
-            }
-    }
-    const int wv = threadIdx.x / WAVE;
-#pragma unroll
-    for (int k = 0; k < XL_NN_MAX; ++k)
-        if (k < nn) {
-            const double ta = wave_sum(a[k]), tb = wave_sum(b[k]);
-            if ((threadIdx.x & (WAVE - 1)) == 0) {
-                sa[wv][k] = ta;
-                sb[wv][k] = tb;
-            }
-        }
-    __syncthreads();
-    if (threadIdx.x < nn) {
-        const int k = threadIdx.x;
-        double ta = 0.0, tb = 0.0;
-        const int nwb = (int)(blockDim.x / WAVE);
-        for (int u = 0; u < nwb; ++u) {
-            ta += sa[u][k];
-            tb += sb[u][k];
-        }
-        xbs[k] = ta;
-        if (blockIdx.x == 0) {
-            const int g0 = st.node_of[(int64_t)st.nonant_depth[k] * S];
-            node_buf[g0 * st.nlen_max + st.nonant_off[k]] = ta;
-            node_buf[half + g0 * st.nlen_max + st.nonant_off[k]] = tb;
-        }
-    }
-    __syncthreads();
-    double acc = 0.0;
-    if (s < S) {
-#pragma unroll
-        for (int k = 0; k < XL_PF; ++k)
-            if (k < nn) {
-                const double xb = xbs[k];
-                xbar[IX(k)] = xb;
-                if (update_W) W[IX(k)] = wo[k] + rv[k] * (xv[k] - xb);
-                acc += fabs(xv[k] - xb);
-            }
-        for (int k = XL_PF; k < nn; ++k) {
-            const double xb = xbs[k];
-            const double xw = x[IX(st.nonant_col[k])];
-            xbar[IX(k)] = xb;
-            if (update_W) W[IX(k)] += rho[IX(k)] * (xw - xb);
-            acc += fabs(xw - xb);
-        }
-    }
-    conv_last_block(acc, o);
-}
-
-// spopt.py:310-439 local sums: prob*obj, prob*bound, prob, prob*feasible, prob*optimal.
-__global__ void __launch_bounds__(BLOCK)
-k_expect_partial(phgpu_state st, const double* __restrict__ obj, const double* __restrict__ bound,
-                 const int32_t* __restrict__ status) {
-    const int64_t S = st.S;
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    if (s < S) {
-        const double p = st.prob[s];
-        v[0] = p * obj[s];
-        v[1] = p * bound[s];
-        v[2] = p;
-        v[3] = (status[s] == PHGPU_OPTIMAL || status[s] == PHGPU_ITER_LIMIT) ? p : 0.0;
-        v[4] = (status[s] == PHGPU_OPTIMAL) ? p : 0.0;
-    }
-#pragma unroll
-    for (int t = 0; t < 5; ++t) {
-        const double a = wave_sum(v[t]);
-        if ((threadIdx.x & (WAVE - 1)) == 0) st.part[(s / WAVE) * 5 + t] = a;
-    }
-}
+// (kernels and device helpers; their entry points are under "C-ABI" below)
+#include "ph_reduce.inc"
 
 // Xhat_Eval._fix_nonants (utils/xhat_eval.py; spopt.py _fix_nonants): nonant columns of
 // every scenario get lb = ub = xfix[k, s] (scaled); xfix == NULL restores the model bounds.
@@ -2124,27 +1032,6 @@ k_fix_nonants(phgpu_state st, const double* __restrict__ xfix) {
             st.ubh[IX(j)] = st.ub[IX(j)] / d;
         }
     }
-}
-
-// Deterministic ordered sum of K interleaved per-wave partials: out[k] = sum_w part[w*K+k].
-// With stats_src / stats_dst (phgpu_ph_update_ex) block 0 also copies a solve's six
-// statistics (a store to host memory here saves a copy launch per PH iteration).
-__global__ void __launch_bounds__(256) k_sum_partials(const double* __restrict__ part, int64_t nw, int K,
-                                                     double scale, double* __restrict__ out,
-                                                     const unsigned long long* __restrict__ stats_src = nullptr,
-                                                     int64_t* __restrict__ stats_dst = nullptr) {
-    __shared__ double sh[256];
-    const int k = blockIdx.x;
-    if (stats_dst && k == 0 && threadIdx.x < 6) stats_dst[threadIdx.x] = (int64_t)stats_src[threadIdx.x];  // (one copy)
-    double a = 0.0;
-    for (int64_t w = threadIdx.x; w < nw; w += 256) a += part[w * K + k];
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[k] = sh[0] * scale;
 }
 
 // ------------------------------------------------------------------ lane plan (host)
@@ -3842,6 +2729,65 @@ static phgpu_state xp_view(const phgpu_state* h, int k) {  // the state with par
 }
 static phgpu_state xp_view(const phgpu_state* h) { return xp_view(h, h->wslot); }
 
+// one tree node whose every plane entry is a nonant's (two-stage problems): every wave is
+// uniform and k_node_final's fast path stores each entry, so the planes need no clearing
+static int assign_ok(const phgpu_state* h) { return (h->num_nodes == 1 && h->nlen_max == h->nn) ? 1 : 0; }
+
+static int two_stage_only(phgpu_state* h, const char* who) {
+    if (h->depth != 1 || h->num_nodes != 1)
+        return set_err(-3, "%s: two-stage handles only (depth %d, %d nodes)", who, h->depth, h->num_nodes);
+    return 0;
+}
+
+// A reduction's workspace at its first use: both buffers or neither.  wave_ws: per-wave
+// partials of nv planes and node tags; ticket_ws: npart per-block partials and the (zeroed)
+// last-block counter.
+static int ws_alloc(phgpu_state* h, ph_ws& w, size_t npart, size_t ntag) {
+    int rc = dalloc(h, &w.part, npart);
+    if (!rc) rc = dalloc(h, &w.tag, ntag);
+    if (rc && w.part) {
+        (void)hipFree(w.part);
+        w.part = nullptr;
+    }
+    return rc;
+}
+static int wave_ws(phgpu_state* h, ph_ws& w, int nv) {
+    const size_t cnt = (size_t)h->nwaves * (size_t)h->nn;
+    return w.part ? 0 : ws_alloc(h, w, cnt * nv, cnt);
+}
+static int ticket_ws(phgpu_state* h, ph_ws& w, size_t npart, hipStream_t st) {
+    if (w.part) return 0;
+    const int rc = ws_alloc(h, w, npart, 1);
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(w.tag, 0, sizeof(int32_t), st));
+    return 0;
+}
+
+// The planes of a node-segmented reduction from its per-wave partials in w: cleared to their
+// identities (and extra, one more plane if given, to 0) unless every entry is stored, then
+// partial (the caller's launch of its partial kernel) and k_node_final
+template <int MAXMASK, int NV, typename Partial>
+static int node_reduce(phgpu_state* h, ph_ws& w, double* planes, double* extra, hipStream_t st, Partial partial) {
+    const int64_t half = (int64_t)h->num_nodes * h->nlen_max;
+    const int assign = assign_ok(h);
+    if (!assign) {
+        const int64_t nex = extra ? half : 0;
+        const int64_t nblk = std::max<int64_t>(1, std::min<int64_t>((NV * half + nex + 255) / 256, 256));
+        hipLaunchKernelGGL((k_planes_clear<MAXMASK, NV>), dim3((unsigned)nblk), dim3(256), 0, st, planes, half, extra,
+                           nex);
+        HIPCHK(hipGetLastError());
+    }
+    if (h->nn == 0) return 0;
+    const int rc = wave_ws(h, w, NV);
+    if (rc) return rc;
+    partial();
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL((k_node_final<MAXMASK, NV>), dim3(h->nn), dim3(XF_THREADS), 0, st, *h, (const double*)w.part,
+                       (const int32_t*)w.tag, planes, assign);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 extern "C" int phgpu_ph_reduce(phgpu_handle h, const double* x, double* node_buf, void* stream) {
     if (!h || !x || !node_buf) return set_err(-1, "null argument");
     FLUSH_STEP(h);
@@ -3855,7 +2801,7 @@ extern "C" int phgpu_ph_reduce(phgpu_handle h, const double* x, double* node_buf
     if (k >= 0) {
         // the solve's epilogue wrote the per-chunk partials: final sums.  With one tree node
         // every node_buf entry is a nonant's (its block stores it); else clear it first
-        const int assign = (h->num_nodes == 1 && h->nlen_max == h->nn) ? 1 : 0;
+        const int assign = assign_ok(h);
         if (!assign) HIPCHK(hipMemsetAsync(node_buf, 0, nb * sizeof(double), st));
         hipLaunchKernelGGL(k_xbar_final, dim3(h->nn), dim3(XF_THREADS), 0, st, xp_view(h, k), node_buf,
                            (const int32_t*)h->xp_dirty[k], h->xp_C[k], x, assign);
@@ -3996,35 +2942,13 @@ extern "C" int phgpu_ph_residuals(phgpu_handle h, const double* x, const double*
     if (!h || !x || !xbar || !rho || !planes || !rho_last) return set_err(-1, "null argument");
     FLUSH_STEP(h);
     hipStream_t st = (hipStream_t)stream;
-    const int64_t half = (int64_t)h->num_nodes * h->nlen_max;
-    // one tree node whose every entry is a nonant's (two-stage problems): every wave is
-    // uniform, so the final sums are stored and the last scenario's lane stores rho_last --
-    // both outputs are overwritten in full without a clearing launch
-    const int assign = (h->num_nodes == 1 && h->nlen_max == h->nn) ? 1 : 0;
-    if (!assign) {
-        hipLaunchKernelGGL(k_resid_clear, dim3((unsigned)std::min<int64_t>((5 * half + 255) / 256, 256)), dim3(256), 0,
-                           st, planes, (int64_t)RS_NV * half, rho_last, half);
-        HIPCHK(hipGetLastError());
-    }
-    if (h->nn == 0) return 0;
-    if (!h->rs_part) {  // first use: workspace of its own (not part / part_node)
-        const size_t cnt = (size_t)h->nwaves * (size_t)h->nn;
-        int rc = dalloc(h, &h->rs_part, cnt * RS_NV);
-        if (!rc) rc = dalloc(h, &h->rs_node, cnt);
-        if (rc) {
-            if (h->rs_part) (void)hipFree(h->rs_part);
-            h->rs_part = nullptr;
-            return rc;
-        }
-    }
-    dim3 g = grid_for(h->S);
-    g.y = (unsigned)h->nn;
-    hipLaunchKernelGGL(k_resid_partial, g, dim3(BLOCK), 0, st, *h, x, xbar, rho, planes, rho_last);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_resid_final<0>, dim3(h->nn), dim3(XF_THREADS), 0, st, *h, (const double*)h->rs_part,
-                       (const int32_t*)h->rs_node, planes, assign);
-    HIPCHK(hipGetLastError());
-    return 0;
+    // (when nothing is cleared, assign_ok, the last scenario's lane stores rho_last: both
+    // outputs are overwritten in full)
+    return node_reduce<0, RS_NV>(h, h->rs, planes, rho_last, st, [&] {
+        dim3 g = grid_for(h->S);
+        g.y = (unsigned)h->nn;
+        hipLaunchKernelGGL(k_resid_partial, g, dim3(BLOCK), 0, st, *h, x, xbar, rho, planes, rho_last);
+    });
 }
 
 // norm_rho_updater.py:128-143
@@ -4048,58 +2972,25 @@ extern "C" int phgpu_nonant_stats(phgpu_handle h, const double* v, double* plane
     if (!h || !v || !planes) return set_err(-1, "null argument");
     FLUSH_STEP(h);
     hipStream_t st = (hipStream_t)stream;
-    const int64_t half = (int64_t)h->num_nodes * h->nlen_max;
-    // one tree node whose every entry is a nonant's: every wave is uniform and the final
-    // kernel stores all four planes in full (as phgpu_ph_residuals' assign)
-    const int assign = (h->num_nodes == 1 && h->nlen_max == h->nn) ? 1 : 0;
-    if (!assign) {
-        hipLaunchKernelGGL(k_nstats_clear, dim3((unsigned)std::min<int64_t>((RS_NV * half + 255) / 256, 256)),
-                           dim3(256), 0, st, planes, half);
-        HIPCHK(hipGetLastError());
-    }
-    if (h->nn == 0) return 0;
-    if (!h->ns_part) {  // first use: workspace of its own
-        const size_t cnt = (size_t)h->nwaves * (size_t)h->nn;
-        int rc = dalloc(h, &h->ns_part, cnt * RS_NV);
-        if (!rc) rc = dalloc(h, &h->ns_node, cnt);
-        if (rc) {
-            if (h->ns_part) (void)hipFree(h->ns_part);
-            h->ns_part = nullptr;
-            return rc;
-        }
-    }
-    dim3 g = grid_for(h->S);
-    g.y = (unsigned)((h->nn + NS_KU - 1) / NS_KU);
-    hipLaunchKernelGGL(k_nstats_partial, g, dim3(BLOCK), 0, st, *h, v, planes);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_resid_final<0xC>, dim3(h->nn), dim3(XF_THREADS), 0, st, *h, (const double*)h->ns_part,
-                       (const int32_t*)h->ns_node, planes, assign);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return node_reduce<0xC, RS_NV>(h, h->ns, planes, nullptr, st, [&] {
+        dim3 g = grid_for(h->S);
+        g.y = (unsigned)((h->nn + NS_KU - 1) / NS_KU);
+        hipLaunchKernelGGL(k_nstats_partial, g, dim3(BLOCK), 0, st, *h, v, planes);
+    });
 }
 
 // extensions/xhatclosest.py:37-51
 extern "C" int phgpu_nonant_closest(phgpu_handle h, const double* v, const double* xbar_node,
                                     const double* xsqbar_node, double* dist, double* best, void* stream) {
     if (!h || !v || !xbar_node || !xsqbar_node || !best) return set_err(-1, "null argument");
-    if (h->depth != 1 || h->num_nodes != 1)
-        return set_err(-3, "phgpu_nonant_closest: two-stage handles only (depth %d, %d nodes)", h->depth,
-                       h->num_nodes);
+    if (two_stage_only(h, "phgpu_nonant_closest")) return -3;
     FLUSH_STEP(h);
     hipStream_t st = (hipStream_t)stream;
     const int64_t nblk = (h->S + NC_T - 1) / NC_T;
-    if (!h->nc_part) {  // first use: the block pairs and the (zeroed) last-block counter
-        int rc = dalloc(h, &h->nc_part, (size_t)(2 * nblk));
-        if (!rc) rc = dalloc(h, &h->nc_cnt, 1);
-        if (rc) {
-            if (h->nc_part) (void)hipFree(h->nc_part);
-            h->nc_part = nullptr;
-            return rc;
-        }
-        HIPCHK(hipMemsetAsync(h->nc_cnt, 0, sizeof(int32_t), st));
-    }
+    const int rc = ticket_ws(h, h->nc, (size_t)(2 * nblk), st);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_nonant_closest, dim3((unsigned)nblk), dim3(NC_T), 0, st, *h, v, xbar_node, xsqbar_node, dist,
-                       h->nc_part, h->nc_cnt, best);
+                       h->nc.part, h->nc.tag, best);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -4126,28 +3017,14 @@ extern "C" int phgpu_w_diff(phgpu_handle h, const double* W, double* W_prev, dou
         HIPCHK(hipMemsetAsync(out, 0, sizeof(double), st));
         return 0;
     }
-    if (!h->wd_part) {  // first use: the block sums and the (zeroed) last-block counter
-        int rc = dalloc(h, &h->wd_part, (size_t)WD_BLOCKS);
-        if (!rc) rc = dalloc(h, &h->wd_cnt, 1);
-        if (rc) {
-            if (h->wd_part) (void)hipFree(h->wd_part);
-            h->wd_part = nullptr;
-            return rc;
-        }
-        HIPCHK(hipMemsetAsync(h->wd_cnt, 0, sizeof(int32_t), st));
-    }
+    const int rc = ticket_ws(h, h->wd, (size_t)WD_BLOCKS, st);
+    if (rc) return rc;
     const int64_t tot = (int64_t)h->nn * h->S;
     // four elements per thread before the grid is capped
     const int64_t nblk = std::max<int64_t>(1, std::min<int64_t>((tot + 4 * GR_T - 1) / (4 * GR_T), WD_BLOCKS));
     hipLaunchKernelGGL(k_w_diff, dim3((unsigned)nblk), dim3(GR_T), 0, st, W, W_prev, tot, 1.0 / (double)tot,
-                       h->wd_part, h->wd_cnt, out);
+                       h->wd.part, h->wd.tag, out);
     HIPCHK(hipGetLastError());
-    return 0;
-}
-
-static int two_stage_only(phgpu_state* h, const char* who) {
-    if (h->depth != 1 || h->num_nodes != 1)
-        return set_err(-3, "%s: two-stage handles only (depth %d, %d nodes)", who, h->depth, h->num_nodes);
     return 0;
 }
 
@@ -4158,30 +3035,9 @@ extern "C" int phgpu_rho_ratio_stats(phgpu_handle h, const double* cost, const d
     if (two_stage_only(h, "phgpu_rho_ratio_stats")) return -3;
     FLUSH_STEP(h);
     hipStream_t st = (hipStream_t)stream;
-    const int64_t half = (int64_t)h->num_nodes * h->nlen_max;
-    const int assign = h->nlen_max == h->nn ? 1 : 0;
-    if (!assign) {
-        hipLaunchKernelGGL(k_rr_clear, dim3((unsigned)std::min<int64_t>((RR_NV * half + 255) / 256, 256)), dim3(256),
-                           0, st, planes, half);
-        HIPCHK(hipGetLastError());
-    }
-    if (h->nn == 0) return 0;
-    if (!h->rr_part) {  // first use: workspace of its own
-        const size_t cnt = (size_t)h->nwaves * (size_t)h->nn;
-        int rc = dalloc(h, &h->rr_part, cnt * RR_NV);
-        if (!rc) rc = dalloc(h, &h->rr_node, cnt);
-        if (rc) {
-            if (h->rr_part) (void)hipFree(h->rr_part);
-            h->rr_part = nullptr;
-            return rc;
-        }
-    }
-    hipLaunchKernelGGL(k_rho_ratio_partial, grid_for(h->S), dim3(BLOCK), 0, st, *h, cost, x, xbar, gden);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL((k_resid_final<0x6, RR_NV>), dim3(h->nn), dim3(XF_THREADS), 0, st, *h,
-                       (const double*)h->rr_part, (const int32_t*)h->rr_node, planes, assign);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return node_reduce<0x6, RR_NV>(h, h->rr, planes, nullptr, st, [&] {
+        hipLaunchKernelGGL(k_rho_ratio_partial, grid_for(h->S), dim3(BLOCK), 0, st, *h, cost, x, xbar, gden);
+    });
 }
 
 // utils/find_rho.py:150-168, extensions/gradient_extension.py:65-68 and 85-94
@@ -4284,11 +3140,13 @@ extern "C" int phgpu_destroy(phgpu_handle h) {
     if (h->stats_gen) (void)hipFree(h->stats_gen);
     {
         void* more[] = {h->xp[0], h->xp[1], h->xp_node[0], h->xp_node[1], h->xp_dirty[0], h->xp_dirty[1],
-                        h->cpart_blk, h->blk_cnt, h->nb_idx, h->rs_part, h->rs_node,
-                        h->ns_part, h->ns_node, h->nc_part, h->nc_cnt, h->wd_part, h->wd_cnt,
-                        h->rr_part, h->rr_node};
+                        h->cpart_blk, h->blk_cnt, h->nb_idx};
         for (void* p : more)
             if (p) (void)hipFree(p);
+        for (const ph_ws& w : {h->rs, h->ns, h->nc, h->wd, h->rr}) {
+            if (w.part) (void)hipFree(w.part);
+            if (w.tag) (void)hipFree(w.tag);
+        }
     }
     if (!h->shared) {  // warm-start slot 1 (slot 0 is x / y / omega / sk_iters above)
         void* slot1[] = {h->xs[1], h->ys[1], h->oms[1], h->its_s[1]};

@@ -80,8 +80,8 @@ def test_update_ex_host_conv_and_stats(gpu, kernel):
                                      e.W.data_ptr(), e.rho.data_ptr(), 1, e.conv_buf.data_ptr(), e._stream()),
                "phgpu_ph_update")
     conv_dev = float(e.conv_buf.item())
-    # the last-block reduction (a hardware ordering of relaxed atomics, phgpu.hip
-    # conv_last_block) against an independent sum: a block partial read before its swap landed
+    # the last-block reduction (a hardware ordering of relaxed atomics, ph_reduce.inc
+    # last_block_publish / conv_last_block) against an independent sum: a block partial read before its swap landed
     # would be off by a whole block's share (phbase.py:321-343: mean |x - x̄| over nonants)
     nc = torch.as_tensor(e.batch.nonant_col, dtype=torch.long, device=e.device)
     ref = (e.x.index_select(0, nc) - e.xbar[:e.nn]).abs().sum().item() / (e.S * e.nn)

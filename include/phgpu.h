@@ -14,6 +14,8 @@
  *   - Update_W + convergence_diff          mpisppy/phbase.py:293-343 -> phgpu_ph_update
  *   - SPOpt.Ebound / Eobjective / _update_E1 / feas_prob local sums
  *                                          mpisppy/spopt.py:310-439 -> phgpu_expectations
+ *   - Fixer.miditer (counters, decisions, var.fix)
+ *                                          mpisppy/extensions/fixer.py:114-304 -> phgpu_fixer_step
  *
  * The cross-rank sums (the per-node MPI Allreduce of phbase.py:83-87 and the
  * ROOT-comm Allreduce of phbase.py:341) are done by the caller (RCCL all-reduce of
@@ -459,6 +461,54 @@ int phgpu_solve_stats(phgpu_handle h, int64_t* out, void* stream);
  * (spopt.py:557-660, xhatbase.py:199-216).
  *   xfix: device [nn*S] (read during the call only) or NULL */
 int phgpu_fix_nonants(phgpu_handle h, const double* xfix, void* stream);
+
+/* Constants of the Fixer's rule (mpisppy/extensions/fixer.py:52-64). */
+typedef struct {
+    double boundtol;  /* fixeroptions["boundtol"]: xb within this of a bound sits on it */
+    int32_t iter0;    /* 1: the rule of Fixer.iter0 (miditer at PH iteration 1), 0: of Fixer.iterk */
+} phgpu_fixer_params;
+
+/* Fixer.miditer (mpisppy/extensions/fixer.py:314-322) for every local (k, s) in one device
+ * pass: the convergence counters (_update_fix_counts, :114-128), the decisions (iter0
+ * :156-189, iterk :248-279) and the bound rewrite.  With g the scenario's node at k's depth
+ * and o the nonant's offset in the node:
+ *   xb   = node_buf[g * nlen_max + o]            (x̄, first half of the reduced node_buf)
+ *   xsq  = node_buf[half + g * nlen_max + o]     (E[x²], half = num_nodes * nlen_max)
+ *   diff = xb * xb - xsq                         (the product rounded on its own)
+ *   l, u = the scenario's model bounds of the column (original units)
+ * An entry that is fixed already is skipped and its counter left alone (is_fixed, :119, 164,
+ * 257): fixval[k, s] is not NaN, or l == u in the model.
+ *   iter0 != 0 (:169-189): converged iff !(-diff > th² || diff > th²) (non-strict); then the
+ *     first of  nb not None -> xb;  lb not None and xb - l < boundtol -> l;
+ *     ub not None and u - xb < boundtol -> u.  Counters are not touched.
+ *   iter0 == 0: count = (-diff < th² && diff < th²) ? count + 1 : 0 (strict, :124-128); then
+ *     if count > 0 the first of (:263-279)  nb not None and nb <= count -> xb;
+ *     lb not None and lb < count and xb - l < boundtol -> l;
+ *     ub not None and ub < count and u - xb < boundtol -> u.
+ * A lag < 0 is the reference's None; 0 is a valid lag.  A nonant without a tuple is th = 0
+ * with all lags None: never fixed, counter 0.  THIS DEPARTS FROM fixer.py in that the lags are
+ * per nonant (there per nonant and scenario; thresholds are per nonant there too, :88-102).
+ * The value is clipped to [l, u]; a newly fixed entry gets fixval[k, s] and the handle's
+ * working bounds lb = ub = value exactly as phgpu_fix_nonants would write them for that entry
+ * (the following solves of every path see it; phgpu_fix_nonants(NULL) would free it again --
+ * pass fixval as its xfix instead).
+ *   th: device double[nn]; nb, lb, ub: device int32[nn]; count: device int32[nn*S] and
+ *   fixval: device double[nn*S] (NaN = free), both k-major and scenario-fastest like W,
+ *   read and updated in place (stores only where something changed);
+ *   nfix: device int32[num_nodes * nlen_max], overwritten in full: the local entries this call
+ *   newly fixed, per node entry;
+ *   totals: device int64[3], accumulated: [0] entries newly fixed, [1] entries found fixed on
+ *   arrival (counted only when iter0, :199-203), [2] node entries with 0 < nfix < the node's
+ *   local scenarios (the "Variation in fixing across scenarios" test of :217-219 and :302-304,
+ *   made per node entry; never decreases).
+ * Ordered on the stream, never synchronises; its workspace (two int32 per node entry: the
+ * local scenarios, and the counts of a call in flight) is allocated at the first call
+ * (phgpu_workspace_bytes grows only then).  Counts
+ * are integer atomics (one per wave where the wave's scenarios share a node): the same inputs
+ * give the same bits. */
+int phgpu_fixer_step(phgpu_handle h, const phgpu_fixer_params* prm, const double* node_buf,
+                     const double* th, const int32_t* nb, const int32_t* lb, const int32_t* ub,
+                     int32_t* count, double* fixval, int32_t* nfix, int64_t* totals, void* stream);
 
 /* Free the workspace and the handle. */
 int phgpu_destroy(phgpu_handle h);

@@ -241,6 +241,11 @@ struct phgpu_state {
     // last-block counter as tag[0]: nc phgpu_nonant_closest ((distance, index) pairs
     // [2 * blocks]), wd phgpu_w_diff ([WD_BLOCKS]).
     ph_ws rs, ns, nc, wd, rr;
+    // phgpu_fixer_step: the local scenarios of every node entry [num_nodes * nlen_max] and behind
+    // them the newly fixed counts of a call in flight (zero between calls), allocated at its
+    // first call; the former counted again after new scenario data (fx_valid 0)
+    int32_t* fx_nloc;
+    int fx_valid;
 };
 
 #define IX(k) ((size_t)(k) * (size_t)S + (size_t)s)
@@ -1011,6 +1016,7 @@ __global__ void k_stats_copy(const unsigned long long* __restrict__ src, int cop
 // ------------------------------------------------------------------ PH reductions
 // (kernels and device helpers; their entry points are under "C-ABI" below)
 #include "ph_reduce.inc"
+#include "ph_fixer.inc"
 
 // Xhat_Eval._fix_nonants (utils/xhat_eval.py; spopt.py _fix_nonants): nonant columns of
 // every scenario get lb = ub = xfix[k, s] (scaled); xfix == NULL restores the model bounds.
@@ -1863,6 +1869,7 @@ static int set_scenarios_shared(phgpu_state* h, const double* A_val, const doubl
     HIPCHK(cp(h->pcoef, prob_coeff, (size_t)h->depth * Sz));
     HIPCHK(hipMemcpyAsync(h->node_of, node_of, (size_t)h->depth * Sz * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     h->xbar_mixed = -1;
+    h->fx_valid = 0;
     if (h->nb_idx) (void)hipFree(h->nb_idx);
     h->nb_idx = nullptr;
     const int big = std::max(nnz, std::max(n, m));
@@ -2001,6 +2008,7 @@ extern "C" int phgpu_set_scenarios(phgpu_handle h, const double* A_val, const do
     HIPCHK(cp(h->pcoef, prob_coeff, (size_t)h->depth * Sz));
     HIPCHK(hipMemcpyAsync(h->node_of, node_of, (size_t)h->depth * Sz * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     h->xbar_mixed = -1;
+    h->fx_valid = 0;
     if (h->nb_idx) (void)hipFree(h->nb_idx);
     h->nb_idx = nullptr;
     h->wslot = h->wq = 0;
@@ -3091,6 +3099,48 @@ extern "C" int phgpu_fix_nonants(phgpu_handle h, const double* xfix, void* strea
     return 0;
 }
 
+// extensions/fixer.py:114-128 (_update_fix_counts), 131-223 (iter0), 226-304 (iterk)
+extern "C" int phgpu_fixer_step(phgpu_handle h, const phgpu_fixer_params* prm, const double* node_buf,
+                                const double* th, const int32_t* nb, const int32_t* lb, const int32_t* ub,
+                                int32_t* count, double* fixval, int32_t* nfix, int64_t* totals, void* stream) {
+    if (!h || !prm || !node_buf || !th || !nb || !lb || !ub || !count || !fixval || !nfix || !totals)
+        return set_err(-1, "null argument");
+    if (!h->scen_set) return set_err(-1, "phgpu_fixer_step: no scenario data yet");
+    FLUSH_STEP(h);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t half = (int64_t)h->num_nodes * h->nlen_max;
+    if (h->nn == 0) {
+        HIPCHK(hipMemsetAsync(nfix, 0, (size_t)half * sizeof(int32_t), st));
+        return 0;
+    }
+    const dim3 g((unsigned)std::min<int64_t>((h->S + FX_T - 1) / FX_T, FX_BLOCKS), (unsigned)std::min(h->nn, GR_ROWS));
+    if (!h->fx_nloc) {  // {nloc | acc}, acc zero between calls (k_fixer_totals clears what it read)
+        const int rc = dalloc(h, &h->fx_nloc, (size_t)(2 * half));
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync(h->fx_nloc, 0, (size_t)(2 * half) * sizeof(int32_t), st));
+        h->fx_valid = 0;
+    } else if (!h->fx_valid) {
+        HIPCHK(hipMemsetAsync(h->fx_nloc, 0, (size_t)half * sizeof(int32_t), st));
+    }
+    if (!h->fx_valid) {
+        hipLaunchKernelGGL(k_fixer_nloc, g, dim3(FX_T), 0, st, *h, h->fx_nloc);
+        HIPCHK(hipGetLastError());
+        h->fx_valid = 1;
+    }
+    int32_t* acc = h->fx_nloc + half;
+    if (h->shared)
+        hipLaunchKernelGGL(k_fixer_step<true>, g, dim3(FX_T), 0, st, *h, *prm, node_buf, th, nb, lb, ub, count, fixval,
+                           acc, (unsigned long long*)totals);
+    else
+        hipLaunchKernelGGL(k_fixer_step<false>, g, dim3(FX_T), 0, st, *h, *prm, node_buf, th, nb, lb, ub, count,
+                           fixval, acc, (unsigned long long*)totals);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_fixer_totals, dim3(1), dim3(FX_T), 0, st, acc, (const int32_t*)h->fx_nloc, half, nfix,
+                       (long long*)totals);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 #include "comm_rccl.inc"
 
 extern "C" int phgpu_destroy(phgpu_handle h) {
@@ -3140,7 +3190,7 @@ extern "C" int phgpu_destroy(phgpu_handle h) {
     if (h->stats_gen) (void)hipFree(h->stats_gen);
     {
         void* more[] = {h->xp[0], h->xp[1], h->xp_node[0], h->xp_node[1], h->xp_dirty[0], h->xp_dirty[1],
-                        h->cpart_blk, h->blk_cnt, h->nb_idx};
+                        h->cpart_blk, h->blk_cnt, h->nb_idx, h->fx_nloc};
         for (void* p : more)
             if (p) (void)hipFree(p);
         for (const ph_ws& w : {h->rs, h->ns, h->nc, h->wd, h->rr}) {

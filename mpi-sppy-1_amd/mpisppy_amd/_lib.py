@@ -52,6 +52,14 @@ class NormRhoParams(ctypes.Structure):
     ]
 
 
+class FixerParams(ctypes.Structure):
+    """phgpu_fixer_params (include/phgpu.h): the constants of the Fixer's rule."""
+    _fields_ = [
+        ("boundtol", c_dbl),
+        ("iter0", c_i32),
+    ]
+
+
 OPTIMAL, ITER_LIMIT, PRIMAL_INFEASIBLE, DUAL_INFEASIBLE = 0, 1, 2, 3
 SHARED_MATRIX = 1          # phgpu_create2 flag (include/phgpu.h)
 
@@ -66,7 +74,7 @@ EXPORTS = ["phgpu_default_options", "phgpu_create", "phgpu_create2", "phgpu_set_
            "phgpu_ph_loop", "phgpu_stream_info", "phgpu_comm_unique_id", "phgpu_comm_init",
            "phgpu_allreduce_sum", "phgpu_ph_residuals", "phgpu_norm_rho_update",
            "phgpu_nonant_stats", "phgpu_nonant_closest", "phgpu_grad_cost", "phgpu_w_diff",
-           "phgpu_rho_ratio_stats", "phgpu_rho_from_stats"]
+           "phgpu_rho_ratio_stats", "phgpu_rho_from_stats", "phgpu_fixer_step"]
 
 _lib = None
 
@@ -124,6 +132,7 @@ def load(path=None):
     lib.phgpu_w_diff.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp]
     lib.phgpu_rho_ratio_stats.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     lib.phgpu_rho_from_stats.argtypes = [c_vp, c_vp, c_i64, c_dbl, c_vp, c_dbl, c_vp, c_vp, c_vp]
+    lib.phgpu_fixer_step.argtypes = [c_vp, ctypes.POINTER(FixerParams)] + [c_vp] * 10
     lib.phgpu_ipm_info.argtypes = [c_vp, ctypes.POINTER(c_dbl)]
     lib.phgpu_ipm_prof.argtypes = [c_vp, ctypes.POINTER(ctypes.c_ulonglong), c_i64]
     lib.phgpu_ipm_prof.restype = c_i64

@@ -16,6 +16,7 @@ GPU, scenario-fastest ``[k, S]``) and sequences the per-PH-iteration work:
                        SUM / MAX all-reduces + phgpu_rho_from_stats
                                                        (utils/gradient.py, find_rho.py, wtracker.py,
                                                         extensions/gradient_extension.py)
+    fixer           -> phgpu_fixer_step               (extensions/fixer.py:114-304)
 
 All launches go to torch's current stream; host synchronisation happens only where
 the reference needs a host scalar (the convergence test, bounds).
@@ -136,7 +137,8 @@ class PHEngine:
                       "ph_loop": 0, "ph_residuals": 0, "norm_rho_update": 0, "allreduce_resid": 0,
                       "solve_deferred": 0, "nonant_stats": 0, "nonant_closest": 0, "allreduce_stats_sum": 0,
                       "allreduce_stats_max": 0, "grad_cost": 0, "w_diff": 0, "rho_ratio_stats": 0,
-                      "rho_from_stats": 0, "allreduce_wdiff": 0, "allreduce_ratio_sum": 0, "allreduce_ratio_max": 0}
+                      "rho_from_stats": 0, "allreduce_wdiff": 0, "allreduce_ratio_sum": 0, "allreduce_ratio_max": 0,
+                      "fixer_step": 0, "fixer_totals_host": 0}
         # several ranks: the conv all-reduce on a side stream under the next solve (False: on
         # the launch stream ahead of it -- bench.py --no-conv-overlap, the comparison case)
         self.overlap_conv = True
@@ -1044,12 +1046,78 @@ class PHEngine:
         """lb = ub = xfix on the nonant columns of every local scenario (device [nn, S]
         tensor, original units) for the next solves; None restores the model bounds
         (spopt.py:557-660 _fix_nonants / _restore_nonants)."""
+        # what the Fixer fixed stays fixed (``fixer_step``): its values fill the NaN entries of
+        # ``xfix``, and restoring the model bounds restores them for the free entries only
+        held = getattr(self, "fixer_fixval", None)
         if xfix is not None:
             self.xfix = xfix.to(device=self.device, dtype=torch.float64).contiguous()
             assert tuple(self.xfix.shape) == (max(self.nn, 1), self.S), self.xfix.shape
+            if held is not None:
+                self.xfix = torch.where(torch.isnan(self.xfix), held, self.xfix)
         else:
             self.xfix = None
-        _lib.check(self.lib.phgpu_fix_nonants(self.h, _ptr(self.xfix), self._stream()), "phgpu_fix_nonants")
+        arg = self.xfix if self.xfix is not None else held
+        _lib.check(self.lib.phgpu_fix_nonants(self.h, _ptr(arg), self._stream()), "phgpu_fix_nonants")
+
+    # -------------------------------------------------------------- fixer
+    def _fixer_bufs(self):
+        if getattr(self, "fixer_fixval", None) is None:
+            half = self.num_nodes * self.nlen_max
+            shape = (max(self.nn, 1), self.S)
+            self.fixer_count = torch.zeros(shape, dtype=torch.int32, device=self.device)
+            self.fixer_fixval = torch.full(shape, float("nan"), dtype=torch.float64, device=self.device)
+            self.fixer_nfix = torch.zeros(half, dtype=torch.int32, device=self.device)
+            self.fixer_totals = torch.zeros(3, dtype=torch.int64, device=self.device)
+            # local scenarios of every node entry (the library keeps its own for totals[2]),
+            # counted on the host: no device pass, no synchronisation
+            nloc = np.zeros(half, dtype=np.int32)
+            if self.nn:
+                b = self.batch
+                node_of = self.node_of.cpu().numpy().reshape(-1, self.S)
+                idx = (node_of[np.asarray(b.nonant_depth, dtype=np.int64)] * self.nlen_max
+                       + np.asarray(b.nonant_off, dtype=np.int64)[:, None])
+                nloc = np.bincount(idx.ravel(), minlength=half).astype(np.int32)
+            self.fixer_nloc = torch.as_tensor(nloc, device=self.device)
+
+    def fixer_prepare(self):
+        """Allocate the Fixer's state ahead of the first ``fixer_step`` (Fixer.populate calls
+        it after Iter0, so that the PH loop's first miditer only enqueues the pass)."""
+        self._fixer_bufs()
+
+    def fixer_arg(self, a, dtype):
+        """A per-nonant input of ``fixer_step`` as a device [nn] tensor: thresholds (float64)
+        or lags (int32; None or a negative value: the reference's None)."""
+        if torch.is_tensor(a):
+            t = a.to(device=self.device, dtype=dtype).contiguous()
+        elif dtype == torch.int32:
+            t = torch.tensor([-1 if v is None or int(v) < 0 else int(v) for v in a], dtype=dtype, device=self.device)
+        else:
+            t = torch.as_tensor(np.asarray(a, dtype=np.float64), device=self.device)
+        assert t.numel() == self.nn, (t.shape, self.nn)
+        return t
+
+    def fixer_step(self, params, th, nb, lb, ub):
+        """Fixer.miditer on the device (phgpu_fixer_step, fixer.py:114-304) for the current
+        x̄ and E[x²]: the counters ``fixer_count``, the values ``fixer_fixval`` (device [nn, S],
+        NaN = free) and the working bounds of the newly fixed entries; ``fixer_nfix`` (per
+        node entry, this call) and ``fixer_totals`` (accumulated).  ``params``:
+        _lib.FixerParams; th / nb / lb / ub: ``fixer_arg`` tensors.  Device work only."""
+        self._flush_xbar()
+        self._fixer_bufs()
+        self.calls["fixer_step"] += 1
+        _lib.check(self.lib.phgpu_fixer_step(self.h, ctypes.byref(params), _ptr(self.node_buf), _ptr(th), _ptr(nb),
+                                             _ptr(lb), _ptr(ub), _ptr(self.fixer_count), _ptr(self.fixer_fixval),
+                                             _ptr(self.fixer_nfix), _ptr(self.fixer_totals), self._stream()),
+                   "phgpu_fixer_step")
+
+    def fixer_totals_host(self):
+        """(entries newly fixed so far, entries fixed on arrival, node entries that fixed only
+        part of their local scenarios) -- the one read back of the Fixer."""
+        self.calls["fixer_totals_host"] += 1
+        if getattr(self, "fixer_totals", None) is None:
+            return 0, 0, 0
+        t = self.fixer_totals.cpu().tolist()
+        return int(t[0]), int(t[1]), int(t[2])
 
     def fix_nonants_by_node(self, table):
         """Fix every local scenario's nonants at per-node values: ``table`` is a device

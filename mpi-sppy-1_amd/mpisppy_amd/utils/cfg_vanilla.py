@@ -1,6 +1,6 @@
 """Cylinder dict builders (mirrors mpisppy/utils/cfg_vanilla.py:41-495 for the cylinders
 this engine serves: ph_hub, lagrangian_spoke, xhatshuffle_spoke, xhatxbar_spoke,
-slammax_spoke, slammin_spoke; extension_adder and add_wxbar_read_write for the hub's
+slammax_spoke, slammin_spoke; extension_adder, add_fixer and add_wxbar_read_write for the hub's
 extensions).
 
 ``cfg`` is any object with the reference's config attribute names (solver_name,
@@ -17,6 +17,7 @@ from ..cylinders.xhatshufflelooper_bounder import XhatShuffleInnerBound
 from ..convergers.norm_rho_converger import NormRhoConverger
 from ..convergers.primal_dual_converger import PrimalDualConverger
 from ..extensions.extension import MultiExtension
+from ..extensions.fixer import Fixer
 from ..extensions.gradient_extension import Gradient_extension
 from ..extensions.mult_rho_updater import MultRhoUpdater
 from ..extensions.norm_rho_updater import NormRhoUpdater
@@ -200,6 +201,18 @@ def extension_adder(hub_dict, ext_class):
     elif ok["extensions"] != ext_class:
         ok["extension_kwargs"] = {"ext_classes": [ok["extensions"], ext_class]}
         ok["extensions"] = MultiExtension
+    return hub_dict
+
+
+# cfg_vanilla.py:184-191 (cfg.fixer_tol, cfg.id_fix_list_fct; with a batch_creator
+# cfg.fix_arrays, the per-nonant arrays of extensions/fixer.py)
+def add_fixer(hub_dict, cfg):
+    hub_dict = extension_adder(hub_dict, Fixer)
+    fixeroptions = {"verbose": False, "boundtol": cfg.fixer_tol,
+                    "id_fix_list_fct": getattr(cfg, "id_fix_list_fct", None)}
+    if getattr(cfg, "fix_arrays", None) is not None:
+        fixeroptions["fix_arrays"] = cfg.fix_arrays
+    hub_dict["opt_kwargs"]["options"]["fixeroptions"] = fixeroptions
     return hub_dict
 
 

@@ -16,12 +16,21 @@ Config 3 (farmer, 65,536 scenarios, cm = 1, rho = 1) from Iter0 to conv < convth
   mult         MultRhoUpdater with the reference's default options: a host miditer, so the
                non-speculative loop
 
+  fixer        Fixer with the same tuple on every nonant (--fixer-th, --fixer-nb; iter0 tuples
+               without a lag): the counters, decisions and bound rewrite in one device pass
+               between Update_W and the solve; the speculative loop.  Fixing trades optimality
+               for speed: compare its E[obj] with the fixed mode's
+  fixer-idle   the same with a threshold of 0, which never counts or fixes: what the pass costs
+  noop-device  an extension whose miditer does nothing and is marked miditer_on_device: the
+               speculative loop without the PH step folded into the solve, as under the Fixer
+
 and, with --kernels, the HIP-event time of phgpu_ph_residuals and phgpu_norm_rho_update
 next to phgpu_ph_update_ex on the same engine.  Prints one line per mode: PH iterations,
 wall seconds of iterk_loop, mean ms per PH iteration, the final conv and rho range.
 
     python tools/rho_convergence.py [--scens 65536] [--convthresh 1e-3] [--limit 3000]
-                                    [--modes fixed,updater,noop,updater-host,gradient,mult] [--kernels]
+                                    [--modes fixed,updater,noop,updater-host,gradient,mult,fixer,fixer-idle,
+                                             noop-device] [--kernels] [--fixer-th 10] [--fixer-nb 3]
                                     [--order-stat 0.5] [--indep-denom]
 """
 import argparse
@@ -36,9 +45,10 @@ for p in (os.path.join(ROOT, "mpi-sppy-1_amd"), ROOT):
         sys.path.insert(0, p)
 
 
-def make_ph(mode, S, thresh, limit, norm_rho_options, grad_options=None):
+def make_ph(mode, S, thresh, limit, norm_rho_options, grad_options=None, fixer=(10.0, 3)):
     from mpisppy_amd.examples import farmer
     from mpisppy_amd.extensions.extension import Extension
+    from mpisppy_amd.extensions.fixer import Fixer
     from mpisppy_amd.extensions.gradient_extension import Gradient_extension
     from mpisppy_amd.extensions.mult_rho_updater import MultRhoUpdater
     from mpisppy_amd.extensions.norm_rho_updater import NormRhoUpdater
@@ -48,13 +58,20 @@ def make_ph(mode, S, thresh, limit, norm_rho_options, grad_options=None):
         def miditer(self):
             pass
 
+    class NoopDevice(NoopMiditer):
+        miditer_on_device = True
+
     ext = {"fixed": None, "updater": NormRhoUpdater, "noop": NoopMiditer, "updater-host": NormRhoUpdater,
-           "gradient": Gradient_extension, "mult": MultRhoUpdater}[mode]
+           "gradient": Gradient_extension, "mult": MultRhoUpdater, "fixer": Fixer, "fixer-idle": Fixer,
+           "noop-device": NoopDevice}[mode]
+    th = [0.0 if mode == "fixer-idle" else float(fixer[0])] * 3
+    fix_arrays = {"iter0": {"th": th}, "iterk": {"th": th, "nb": [int(fixer[1])] * 3}}
     opts = {"solver_name": "mi355x_pdhg", "PHIterLimit": limit, "defaultPHrho": 1.0, "convthresh": thresh,
             "verbose": False, "display_progress": False, "toc": False, "device": "cuda:0",
             "batch_creator": farmer.batch_creator, "iterk_solver_options": dict(farmer.PDHG_ITERK_OPTIONS),
             "speculative_solve": mode != "updater-host", "norm_rho_options": dict(norm_rho_options),
-            "gradient_extension_options": dict(grad_options or {"order_stat": 0.5})}
+            "gradient_extension_options": dict(grad_options or {"order_stat": 0.5}),
+            "fixeroptions": {"verbose": False, "boundtol": 1e-2, "fix_arrays": fix_arrays}}
     return PH(opts, farmer.scenario_names_creator(S), farmer.scenario_creator, extensions=ext,
               scenario_creator_kwargs={"crops_multiplier": 1, "num_scens": S})
 
@@ -62,7 +79,7 @@ def make_ph(mode, S, thresh, limit, norm_rho_options, grad_options=None):
 def run_mode(mode, a, norm_rho_options):
     import torch
     ph = make_ph(mode, a.scens, a.convthresh, a.limit, norm_rho_options,
-                 {"order_stat": a.order_stat, "indep_denom": a.indep_denom})
+                 {"order_stat": a.order_stat, "indep_denom": a.indep_denom}, (a.fixer_th, a.fixer_nb))
     ph.PH_Prep()
     ph.Iter0()
     torch.cuda.synchronize()
@@ -77,6 +94,11 @@ def run_mode(mode, a, norm_rho_options):
            "conv": float(ph.conv), "rho_min": float(rho.min()), "rho_max": float(rho.max()),
            "speculative": bool(ph._speculate(ph.extensions is not None)),
            "calls": {k: v for k, v in e.calls.items() if v}}
+    if mode.startswith("fixer"):
+        res["fixer_totals"] = list(e.fixer_totals_host())
+        res["nonants_fixed"] = res["fixer_totals"][0] / a.scens
+        if a.kernels:
+            res["kernel_us"] = fixer_kernel_times(e, ph)
     if mode.startswith("updater") and e.calls["norm_rho_update"]:
         res["last_counts"] = e.norm_rho_counts().tolist()
     if mode == "gradient":
@@ -87,8 +109,23 @@ def run_mode(mode, a, norm_rho_options):
         res["kernel_us"] = kernel_times(e, ph)
     if a.kernels and mode == "gradient":
         res["kernel_us"] = grad_kernel_times(e, ph)
+    res["Eobj"] = xbar_objective(ph)
     e.close()
     return res
+
+
+def xbar_objective(ph):
+    """E[f] with every nonant fixed at the final x̄ (W and prox off): what the run's answer is
+    worth, comparable between the modes."""
+    e = ph.engine
+    e._flush_xbar()
+    ph.disable_W_and_prox()
+    e.fix_nonants(e.xbar.clone())
+    e.solve(ph._to_phgpu_options(ph.current_solver_options), warm=True)
+    obj = float(ph.Eobjective())
+    e.fix_nonants(None)
+    ph.reenable_W_and_prox()
+    return obj
 
 
 def kernel_times(e, ph, reps=200):
@@ -125,6 +162,38 @@ def kernel_times(e, ph, reps=200):
     return out
 
 
+def fixer_kernel_times(e, ph, reps=200):
+    """Mean HIP-event microseconds per engine.fixer_step (the nfix clear, the pass and the totals
+    launch) with a threshold of 0, which changes nothing, next to phgpu_ph_update_ex."""
+    import torch
+    from mpisppy_amd import _lib
+    none = e.fixer_arg([None] * e.nn, torch.int32)
+    th = e.fixer_arg([0.0] * e.nn, torch.float64)
+    prm = _lib.FixerParams(boundtol=1e-2, iter0=0)
+    W0 = e.W.clone()
+    conv = torch.zeros(1, dtype=torch.float64, device=e.device)
+    e.compute_xbar()
+
+    def upd():
+        _lib.check(e.lib.phgpu_ph_update_ex(e.h, e.x.data_ptr(), e.node_buf.data_ptr(), e.xbar.data_ptr(),
+                                            e.W.data_ptr(), e.rho.data_ptr(), 1, conv.data_ptr(), None, e._stream()),
+                   "phgpu_ph_update_ex")
+
+    out = {}
+    for name, fn in (("fixer_step", lambda: e.fixer_step(prm, th, none, none, none)), ("phgpu_ph_update_ex", upd)):
+        for _ in range(10):
+            fn()
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+        for _ in range(reps):
+            fn()
+        ev[1].record()
+        ev[1].synchronize()
+        out[name] = 1e3 * ev[0].elapsed_time(ev[1]) / reps
+    e.W.copy_(W0)
+    return out
+
+
 def grad_kernel_times(e, ph, reps=200):
     """Mean HIP-event microseconds per call of engine.w_diff and engine.find_rho (the ratio pass,
     its final sum and the rule, gate closed so rho stays) on this engine's current state."""
@@ -156,6 +225,8 @@ def main():
     p.add_argument("--norm-rho-option", action="append", default=[], metavar="KEY=VALUE")
     p.add_argument("--order-stat", type=float, default=0.5, help="gradient mode: 0 the min, 0.5 the mean, 1 the max")
     p.add_argument("--indep-denom", action="store_true", help="gradient mode: the scenario-independent denominator")
+    p.add_argument("--fixer-th", type=float, default=10.0, help="fixer mode: the threshold of every nonant")
+    p.add_argument("--fixer-nb", type=int, default=3, help="fixer mode: the nb lag of every nonant")
     a = p.parse_args()
     nro = {}
     for kv in a.norm_rho_option:
@@ -172,7 +243,7 @@ def main():
         r = run_mode(mode.strip(), a, nro)
         print(f"# {r['mode']:13s} {r['ph_iterations']:5d} PH iterations  {r['loop_seconds']:8.4f} s  "
               f"{r['ms_per_iteration']:.4f} ms / iteration  conv {r['conv']:.3e}  "
-              f"rho [{r['rho_min']:g}, {r['rho_max']:g}]  converged {r['converged']}", flush=True)
+              f"rho [{r['rho_min']:g}, {r['rho_max']:g}]  converged {r['converged']}  E[obj] {r['Eobj']:.6f}", flush=True)
         print(json.dumps(r), flush=True)
 
 

@@ -248,6 +248,90 @@ struct phgpu_state {
     int fx_valid;
 };
 
+// ------------------------------------------------------------------ ownership (host)
+// What phgpu_create2 allocates and phgpu_destroy deletes: the state (the base, which the
+// kernels receive by value, sliced) and what only the host needs.  Every device buffer of
+// the handle comes from dalloc and is in allocs until dfree or phgpu_destroy frees it; the
+// counted ones make up phgpu_workspace_bytes.
+struct dev_alloc {
+    void* p;
+    size_t bytes;
+    bool counted;
+};
+struct phgpu_owner : phgpu_state {
+    std::vector<dev_alloc> allocs;
+    std::string ipm_tuning;  // phgpu_set_ipm_tuning's definitions, normalised ("" none)
+};
+static inline phgpu_owner* owner_of(phgpu_state* h) { return static_cast<phgpu_owner*>(h); }
+
+template <typename T>
+static int dalloc(phgpu_state* h, T** p, size_t count, bool counted = true) {
+    *p = nullptr;
+    if (count == 0) count = 1;
+    const size_t bytes = count * sizeof(T);
+    hipError_t e = hipMalloc((void**)p, bytes);
+    if (e != hipSuccess) return set_err(-3, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+    owner_of(h)->allocs.push_back({(void*)*p, bytes, counted});
+    if (counted) h->ws_bytes += (int64_t)bytes;
+    return 0;
+}
+
+// free one buffer of the handle (null: nothing), give its bytes back if it was counted
+template <typename T>
+static void dfree(phgpu_state* h, T** p) {
+    if (!*p) return;
+    std::vector<dev_alloc>& v = owner_of(h)->allocs;
+    for (size_t i = v.size(); i-- > 0;)
+        if (v[i].p == (void*)*p) {
+            if (v[i].counted) h->ws_bytes -= (int64_t)v[i].bytes;
+            v[i] = v.back();
+            v.pop_back();
+            break;
+        }
+    (void)hipFree((void*)*p);
+    *p = nullptr;
+}
+
+#define ALLOC(ptr, cnt)                         \
+    do {                                        \
+        int rc_ = dalloc(h, &(ptr), (size_t)(cnt)); \
+        if (rc_) { phgpu_destroy(h); return rc_; } \
+    } while (0)
+
+// a host vector on the device: a (counted) buffer of the handle and the copy into it
+template <typename T>
+static int dupload(phgpu_state* h, T** d, const std::vector<T>& v, const char* what) {
+    const int rc = dalloc(h, d, v.size());
+    if (rc) return rc;
+    const hipError_t e = v.empty() ? hipSuccess : hipMemcpy(*d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return set_err(-2, "%s upload failed: %s", what, hipGetErrorString(e));
+    return 0;
+}
+
+// a temporary device buffer of one call, freed by release() or on any other exit
+template <typename T>
+struct dev_tmp {
+    T* p = nullptr;
+    dev_tmp() = default;
+    dev_tmp(const dev_tmp&) = delete;
+    dev_tmp& operator=(const dev_tmp&) = delete;
+    ~dev_tmp() { release(); }
+    hipError_t alloc(size_t count) { return hipMalloc((void**)&p, count * sizeof(T)); }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+};
+
+// unload a hipRTC module of the handle (jit_module, ipm_module) and delete its record
+template <typename M>
+static void module_release(M*& m) {
+    if (!m) return;
+    if (m->mod) (void)hipModuleUnload(m->mod);
+    delete m;
+    m = nullptr;
+}
+
 #define IX(k) ((size_t)(k) * (size_t)S + (size_t)s)
 
 // ------------------------------------------------------------------ device helpers
@@ -1233,22 +1317,6 @@ static bool build_wg_plan(const wg_instance& g, int n, int m, const int32_t* row
 }
 
 // ------------------------------------------------------------------ C-ABI
-template <typename T>
-static int dalloc(phgpu_state* h, T** p, size_t count) {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc((void**)p, count * sizeof(T));
-    if (e != hipSuccess) return set_err(-3, "hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e));
-    h->ws_bytes += (int64_t)(count * sizeof(T));
-    return 0;
-}
-
-#define ALLOC(ptr, cnt)                         \
-    do {                                        \
-        int rc_ = dalloc(h, &(ptr), (size_t)(cnt)); \
-        if (rc_) { phgpu_destroy(h); return rc_; } \
-    } while (0)
-
 // ---------------------------------------------------------- scenario-major records
 static hipError_t to_records(phgpu_state* h, const double* in, int K, int off, hipStream_t st) {
     if (K <= 0) return hipSuccess;
@@ -1393,18 +1461,12 @@ static int sell_one(phgpu_state* h, int K, const std::vector<int32_t>& ptr, cons
         wslc.insert(wslc.end(), lists[w].begin(), lists[w].end());
         wptr[w + 1] = (int32_t)wslc.size();
     }
-    if (dalloc(h, d_off, off.size()) || dalloc(h, d_len, len.size()) || dalloc(h, d_idx, e_idx.size()) ||
-        dalloc(h, d_src, e_src.size()) || dalloc(h, d_val, e_idx.size()) || dalloc(h, d_wptr, wptr.size()) ||
-        dalloc(h, d_wslc, std::max<size_t>(wslc.size(), 1)))
-        return -3;
-    hipError_t e = hipMemcpy(*d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(*d_len, len.data(), std::max<size_t>(len.size(), 1) * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(*d_idx, e_idx.data(), e_idx.size() * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(*d_src, e_src.data(), e_src.size() * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(*d_wptr, wptr.data(), wptr.size() * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !wslc.empty()) e = hipMemcpy(*d_wslc, wslc.data(), wslc.size() * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return set_err(-2, "sliced-ELL upload failed: %s", hipGetErrorString(e));
-    return 0;
+    struct { int32_t** d; const std::vector<int32_t>* v; } up[] = {
+        {d_off, &off}, {d_len, &len}, {d_idx, &e_idx}, {d_src, &e_src}, {d_wptr, &wptr}, {d_wslc, &wslc}};
+    int rc = dalloc(h, d_val, e_idx.size());
+    for (auto& u : up)
+        if (!rc) rc = dupload(h, u.d, *u.v, "sliced-ELL");
+    return rc;
 }
 
 static int build_sell(phgpu_state* h, const int32_t* row_ptr, const int32_t* col_idx) {
@@ -1429,6 +1491,91 @@ static int build_sell(phgpu_state* h, const int32_t* row_ptr, const int32_t* col
         }
     return sell_one(h, n, cp, ri, csrc, h->nsl_c, h->nent_c, &h->cs_off, &h->cs_len, &h->cs_idx, &h->cs_src, &h->cs_val,
                     &h->cw_ptr, &h->cw_slc);
+}
+
+// several plan vectors onto the device; an allocation failure as "<what> allocation failed"
+struct plan_upload {
+    int32_t** d;
+    const std::vector<int32_t>* v;
+};
+static int plan_uploads(phgpu_state* h, const plan_upload* up, int cnt, const char* what) {
+    int rc = 0;
+    for (int k = 0; k < cnt && !rc; ++k) rc = dupload(h, up[k].d, *up[k].v, what);
+    if (rc == -3) return set_err(-3, "%s allocation failed", what);
+    return rc;
+}
+
+// register-resident path: lanes per scenario L (power of two <= 64): the smallest L
+// with a fitting instance, doubled while S * L lanes would not fill REG_WAVES_PER_EU
+// waves on every SIMD of the chip and a scenario still has columns to spread
+// (measured on farmer cm=1: L=4 at S >= 32768, 8 at 16384, 16 at 8192 -- profiles/r01),
+// and past any L whose instance spills (reg_spills);
+// PHGPU_LANES=<L> pins it (tuning / tests)
+static int reg_plan_select(phgpu_state* h, const int32_t* row_ptr, const int32_t* col_idx) {
+    const int n = h->n, m = h->m;
+    const int64_t target = (int64_t)h->num_cus * 4 * WAVE * REG_WAVES_PER_EU;
+    const char* env = getenv("PHGPU_LANES");
+    const int pinned = env ? atoi(env) : 0;
+    int chosen = -1;
+    bool chosen_spills = false;
+    std::vector<int32_t> ck, cr, rk, rc;
+    int inst = -1, kc = 0, zc = 0, kr = 0, zr = 0;
+    for (int L = 1; L <= WAVE; L *= 2) {
+        if (pinned > 0 && L != pinned) continue;
+        std::vector<int32_t> a1, a2, a3, a4;
+        int i1, i2, i3, i4, i5;
+        if (!build_plan(L, n, m, row_ptr, col_idx, &i1, &i2, &i3, &i4, &i5, a1, a2, a3, a4)) continue;
+        if (pinned <= 0 && chosen >= 0 && (h->S * (int64_t)chosen >= target || chosen >= n) &&
+            !chosen_spills)
+            break;
+        chosen = L;
+        chosen_spills = reg_spills(g_reg_instances[i1]);
+        inst = i1; kc = i2; zc = i3; kr = i4; zr = i5;
+        ck.swap(a1); cr.swap(a2); rk.swap(a3); rc.swap(a4);
+    }
+    if (chosen <= 0) return 0;
+    const plan_upload up[] = {{&h->pl_col_k, &ck}, {&h->pl_col_r, &cr}, {&h->pl_row_k, &rk}, {&h->pl_row_c, &rc}};
+    const int rcu = plan_uploads(h, up, 4, "plan");
+    if (rcu) return rcu;
+    h->reg_inst = inst;
+    h->reg_L = chosen;
+    h->reg_kc = kc;
+    h->reg_zc = zc;
+    h->reg_kr = kr;
+    h->reg_zr = zr;
+    return 0;
+}
+
+// workgroup-per-scenario path: the cheapest non-spilling instance by slot_cost x waves
+// per scenario (PHGPU_WPS=<waves> pins the waves per scenario); *best = its cost
+static int wg_plan_select(phgpu_state* h, const int32_t* row_ptr, const int32_t* col_idx, long* best) {
+    const char* env = getenv("PHGPU_WPS");
+    const int pinned = env ? atoi(env) : 0;
+    const int ninst = (int)(sizeof(g_wg_instances) / sizeof(g_wg_instances[0]));
+    wg_plan_host bp;
+    *best = 0;
+    for (int a = 0; a < ninst; ++a) {
+        const wg_instance& g = g_wg_instances[a];
+        if (pinned > 0 && g.WPS != pinned) continue;
+        wg_plan_host p;
+        if (!build_wg_plan(g, h->n, h->m, row_ptr, col_idx, p)) continue;
+        if (wg_spills(g)) continue;
+        const long cost = (long)g.WPS * slot_cost(g.KC, g.ZC, g.KR, g.ZR, p.long_per_wave);
+        if (h->wg_inst < 0 || cost < *best) {
+            h->wg_inst = a;
+            *best = cost;
+            bp = std::move(p);
+        }
+    }
+    if (h->wg_inst < 0) return 0;
+    const plan_upload up[] = {{&h->wg_col_id, &bp.col_id},     {&h->wg_row_id, &bp.row_id},
+                              {&h->wg_col_long, &bp.col_long}, {&h->wg_row_long, &bp.row_long},
+                              {&h->wg_col_k, &bp.col_k},       {&h->wg_col_r, &bp.col_r},
+                              {&h->wg_row_k, &bp.row_k},       {&h->wg_row_c, &bp.row_c}};
+    const int rc = plan_uploads(h, up, 8, "workgroup plan");
+    if (rc) return rc;
+    h->wg_long = bp.nlong;
+    return 0;
 }
 
 static int step_local_impl(phgpu_state* h, const double* x, double* node_buf, double* xbar, double* W,
@@ -1500,24 +1647,18 @@ extern "C" int phgpu_create2(phgpu_handle* out, int device, int64_t S, int32_t n
         if (row_ptr[i + 1] < row_ptr[i]) return set_err(-1, "row_ptr not monotone at row %d", i);
     for (int k = 0; k < nnz; ++k)
         if (col_idx[k] < 0 || col_idx[k] >= n) return set_err(-1, "col_idx[%d]=%d out of range", k, col_idx[k]);
-    int32_t* slot = new int32_t[n];
-    for (int j = 0; j < n; ++j) slot[j] = -1;
+    std::vector<int32_t> slot((size_t)n, -1);
     for (int k = 0; k < nn; ++k) {
         if (nonant_col[k] < 0 || nonant_col[k] >= n || slot[nonant_col[k]] >= 0 ||
             nonant_depth[k] < 0 || nonant_depth[k] >= depth || nonant_off[k] < 0 ||
-            nonant_off[k] >= nlen_max) {
-            delete[] slot;
+            nonant_off[k] >= nlen_max)
             return set_err(-1, "bad nonant map at %d", k);
-        }
         slot[nonant_col[k]] = k;
     }
     HIPCHK(hipSetDevice(device));
-    phgpu_state* h = new (std::nothrow) phgpu_state();
-    if (!h) {
-        delete[] slot;
-        return set_err(-3, "out of host memory");
-    }
-    memset(h, 0, sizeof(*h));
+    phgpu_state* h = new (std::nothrow) phgpu_owner();
+    if (!h) return set_err(-3, "out of host memory");
+    memset(h, 0, sizeof(phgpu_state));  // the state only: the owner's members stay constructed
     h->last_rec = -1;
     h->device = device;
     h->S = S;
@@ -1531,15 +1672,11 @@ extern "C" int phgpu_create2(phgpu_handle* out, int device, int64_t S, int32_t n
     h->nwaves = (S + WAVE - 1) / WAVE;
     h->xbar_mixed = -1;
     // transposed pattern (host)
-    int32_t* cptr = new int32_t[n + 1]();
-    int32_t* ridx = new int32_t[nnz > 0 ? nnz : 1];
-    int32_t* perm = new int32_t[nnz > 0 ? nnz : 1];
-    int32_t* rowof = new int32_t[nnz > 0 ? nnz : 1];
+    std::vector<int32_t> cptr((size_t)n + 1, 0), ridx((size_t)nnz), perm((size_t)nnz), rowof((size_t)nnz);
     for (int k = 0; k < nnz; ++k) cptr[col_idx[k] + 1]++;
     for (int j = 0; j < n; ++j) cptr[j + 1] += cptr[j];
     {
-        int32_t* fill = new int32_t[n];
-        for (int j = 0; j < n; ++j) fill[j] = cptr[j];
+        std::vector<int32_t> fill(cptr.begin(), cptr.end() - 1);
         for (int i = 0; i < m; ++i)
             for (int k = row_ptr[i]; k < row_ptr[i + 1]; ++k) {
                 const int p = fill[col_idx[k]]++;
@@ -1547,10 +1684,8 @@ extern "C" int phgpu_create2(phgpu_handle* out, int device, int64_t S, int32_t n
                 perm[p] = k;
                 rowof[k] = i;
             }
-        delete[] fill;
     }
     const size_t Sz = (size_t)S;
-    int rc = 0;
     ALLOC(h->row_ptr, m + 1);
     ALLOC(h->col_idx, nnz);
     ALLOC(h->col_ptr, n + 1);
@@ -1691,140 +1826,33 @@ extern "C" int phgpu_create2(phgpu_handle* out, int device, int64_t S, int32_t n
             return set_err(-2, "hipMemset failed");
         }
     }
-    (void)rc;
     hipError_t e = hipSuccess;
     e = hipMemcpy(h->row_ptr, row_ptr, (m + 1) * sizeof(int32_t), hipMemcpyHostToDevice);
     if (e == hipSuccess && nnz) e = hipMemcpy(h->col_idx, col_idx, nnz * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(h->col_ptr, cptr, (n + 1) * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess && nnz) e = hipMemcpy(h->row_idx, ridx, nnz * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess && nnz) e = hipMemcpy(h->perm, perm, nnz * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess && nnz) e = hipMemcpy(h->row_of, rowof, nnz * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(h->col_ptr, cptr.data(), (n + 1) * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess && nnz) e = hipMemcpy(h->row_idx, ridx.data(), nnz * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess && nnz) e = hipMemcpy(h->perm, perm.data(), nnz * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess && nnz) e = hipMemcpy(h->row_of, rowof.data(), nnz * sizeof(int32_t), hipMemcpyHostToDevice);
     if (e == hipSuccess && nn) e = hipMemcpy(h->nonant_col, nonant_col, nn * sizeof(int32_t), hipMemcpyHostToDevice);
     if (e == hipSuccess && nn) e = hipMemcpy(h->nonant_depth, nonant_depth, nn * sizeof(int32_t), hipMemcpyHostToDevice);
     if (e == hipSuccess && nn) e = hipMemcpy(h->nonant_off, nonant_off, nn * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(h->nonant_slot, slot, n * sizeof(int32_t), hipMemcpyHostToDevice);
-    delete[] cptr;
-    delete[] ridx;
-    delete[] perm;
-    delete[] rowof;
-    delete[] slot;
+    if (e == hipSuccess) e = hipMemcpy(h->nonant_slot, slot.data(), n * sizeof(int32_t), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         phgpu_destroy(h);
         return set_err(-2, "pattern upload failed: %s", hipGetErrorString(e));
     }
-    // register-resident path: lanes per scenario L (power of two <= 64): the smallest L
-    // with a fitting instance, doubled while S * L lanes would not fill REG_WAVES_PER_EU
-    // waves on every SIMD of the chip and a scenario still has columns to spread
-    // (measured on farmer cm=1: L=4 at S >= 32768, 8 at 16384, 16 at 8192 -- profiles/r01),
-    // and past any L whose instance spills (reg_spills);
-    // PHGPU_LANES=<L> pins it (tuning / tests)
     h->reg_inst = -1;
     h->wg_inst = -1;
+    long best = 0;
+    int rcp = 0;
     if (h->shared) {
-        const int rcs = build_sell(h, row_ptr, col_idx);
-        if (rcs) {
-            phgpu_destroy(h);
-            return rcs;
-        }
+        rcp = build_sell(h, row_ptr, col_idx);
         h->default_kernel = 4;
-        *out = h;
-        return 0;
+    } else {
+        rcp = reg_plan_select(h, row_ptr, col_idx);
+        if (!rcp) rcp = wg_plan_select(h, row_ptr, col_idx, &best);
     }
-    {
-        const int64_t target = (int64_t)h->num_cus * 4 * WAVE * REG_WAVES_PER_EU;
-        const char* env = getenv("PHGPU_LANES");
-        const int pinned = env ? atoi(env) : 0;
-        int chosen = -1;
-        bool chosen_spills = false;
-        std::vector<int32_t> ck, cr, rk, rc;
-        int inst = -1, kc = 0, zc = 0, kr = 0, zr = 0;
-        for (int L = 1; L <= WAVE; L *= 2) {
-            if (pinned > 0 && L != pinned) continue;
-            std::vector<int32_t> a1, a2, a3, a4;
-            int i1, i2, i3, i4, i5;
-            if (!build_plan(L, n, m, row_ptr, col_idx, &i1, &i2, &i3, &i4, &i5, a1, a2, a3, a4)) continue;
-            if (pinned <= 0 && chosen >= 0 && (S * (int64_t)chosen >= target || chosen >= n) &&
-                !chosen_spills)
-                break;
-            chosen = L;
-            chosen_spills = reg_spills(g_reg_instances[i1]);
-            inst = i1; kc = i2; zc = i3; kr = i4; zr = i5;
-            ck.swap(a1); cr.swap(a2); rk.swap(a3); rc.swap(a4);
-        }
-        if (chosen > 0) {
-            int rc2 = 0;
-            rc2 |= dalloc(h, &h->pl_col_k, ck.size());
-            rc2 |= dalloc(h, &h->pl_col_r, cr.size());
-            rc2 |= dalloc(h, &h->pl_row_k, rk.size());
-            rc2 |= dalloc(h, &h->pl_row_c, rc.size());
-            if (rc2) {
-                phgpu_destroy(h);
-                return set_err(-3, "plan allocation failed");
-            }
-            e = hipMemcpy(h->pl_col_k, ck.data(), ck.size() * 4, hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(h->pl_col_r, cr.data(), cr.size() * 4, hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(h->pl_row_k, rk.data(), rk.size() * 4, hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(h->pl_row_c, rc.data(), rc.size() * 4, hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                phgpu_destroy(h);
-                return set_err(-2, "plan upload failed: %s", hipGetErrorString(e));
-            }
-            h->reg_inst = inst;
-            h->reg_L = chosen;
-            h->reg_kc = kc;
-            h->reg_zc = zc;
-            h->reg_kr = kr;
-            h->reg_zr = zr;
-        }
-    }
-    // workgroup-per-scenario path: the cheapest non-spilling instance by slot_cost x waves
-    // per scenario (PHGPU_WPS=<waves> pins the waves per scenario)
-    h->wg_inst = -1;
-    {
-        const char* env = getenv("PHGPU_WPS");
-        const int pinned = env ? atoi(env) : 0;
-        const int ninst = (int)(sizeof(g_wg_instances) / sizeof(g_wg_instances[0]));
-        long best = 0;
-        wg_plan_host bp;
-        for (int a = 0; a < ninst; ++a) {
-            const wg_instance& g = g_wg_instances[a];
-            if (pinned > 0 && g.WPS != pinned) continue;
-            wg_plan_host p;
-            if (!build_wg_plan(g, n, m, row_ptr, col_idx, p)) continue;
-            if (wg_spills(g)) continue;
-            const long cost = (long)g.WPS * slot_cost(g.KC, g.ZC, g.KR, g.ZR, p.long_per_wave);
-            if (h->wg_inst < 0 || cost < best) {
-                h->wg_inst = a;
-                best = cost;
-                bp = std::move(p);
-            }
-        }
-        if (h->wg_inst >= 0) {
-            int rc2 = 0;
-            rc2 |= dalloc(h, &h->wg_col_id, bp.col_id.size());
-            rc2 |= dalloc(h, &h->wg_row_id, bp.row_id.size());
-            rc2 |= dalloc(h, &h->wg_col_long, bp.col_long.size());
-            rc2 |= dalloc(h, &h->wg_row_long, bp.row_long.size());
-            rc2 |= dalloc(h, &h->wg_col_k, bp.col_k.size());
-            rc2 |= dalloc(h, &h->wg_col_r, bp.col_r.size());
-            rc2 |= dalloc(h, &h->wg_row_k, bp.row_k.size());
-            rc2 |= dalloc(h, &h->wg_row_c, bp.row_c.size());
-            if (rc2) {
-                phgpu_destroy(h);
-                return set_err(-3, "workgroup plan allocation failed");
-            }
-            struct { int32_t* d; std::vector<int32_t>* v; } up[] = {
-                {h->wg_col_id, &bp.col_id}, {h->wg_row_id, &bp.row_id}, {h->wg_col_long, &bp.col_long},
-                {h->wg_row_long, &bp.row_long}, {h->wg_col_k, &bp.col_k}, {h->wg_col_r, &bp.col_r},
-                {h->wg_row_k, &bp.row_k}, {h->wg_row_c, &bp.row_c}};
-            for (auto& u : up)
-                if (e == hipSuccess) e = hipMemcpy(u.d, u.v->data(), u.v->size() * 4, hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                phgpu_destroy(h);
-                return set_err(-2, "workgroup plan upload failed: %s", hipGetErrorString(e));
-            }
-            h->wg_long = bp.nlong;
-        }
+    if (!rcp && !h->shared) {
         // default path: the cheaper per scenario (register path at its chosen L)
         long reg_cost_s = -1;
         if (h->reg_inst >= 0) {
@@ -1834,13 +1862,11 @@ extern "C" int phgpu_create2(phgpu_handle* out, int device, int64_t S, int32_t n
         if (h->reg_inst >= 0 && (h->wg_inst < 0 || reg_cost_s <= best)) h->default_kernel = 2;
         else if (h->wg_inst >= 0) h->default_kernel = 3;
         else h->default_kernel = 1;
-        if (h->default_kernel == 3) {
-            const int rc3 = pack_alloc(h);
-            if (rc3) {
-                phgpu_destroy(h);
-                return rc3;
-            }
-        }
+        if (h->default_kernel == 3) rcp = pack_alloc(h);
+    }
+    if (rcp) {
+        phgpu_destroy(h);
+        return rcp;
     }
     *out = h;
     return 0;
@@ -1870,8 +1896,7 @@ static int set_scenarios_shared(phgpu_state* h, const double* A_val, const doubl
     HIPCHK(hipMemcpyAsync(h->node_of, node_of, (size_t)h->depth * Sz * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     h->xbar_mixed = -1;
     h->fx_valid = 0;
-    if (h->nb_idx) (void)hipFree(h->nb_idx);
-    h->nb_idx = nullptr;
+    dfree(h, &h->nb_idx);
     const int big = std::max(nnz, std::max(n, m));
     const dim3 gb((unsigned)((big + 255) / 256)), gn((unsigned)((n + 255) / 256)), gm((unsigned)((m + 255) / 256));
     const dim3 gz((unsigned)((nnz + 255) / 256 > 0 ? (nnz + 255) / 256 : 1));
@@ -1904,17 +1929,17 @@ static int set_scenarios_shared(phgpu_state* h, const double* A_val, const doubl
     hipLaunchKernelGGL(k_sh_base, gb, dim3(256), 0, st, *h, c, q, lb, ub, rl, ru);
     HIPCHK(hipGetLastError());
     // which columns / rows differ between scenarios (one wave per entry)
-    int32_t* flags = nullptr;
-    HIPCHK(hipMalloc((void**)&flags, (size_t)(n + m + 1) * sizeof(int32_t)));
-    hipLaunchKernelGGL(k_sh_vary, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, c, q, lb, ub, n, h->S, flags);
+    dev_tmp<int32_t> flags;
+    HIPCHK(flags.alloc((size_t)(n + m + 1)));
+    hipLaunchKernelGGL(k_sh_vary, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, c, q, lb, ub, n, h->S, flags.p);
     if (m) hipLaunchKernelGGL(k_sh_vary, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, rl, ru, (const double*)nullptr,
-                              (const double*)nullptr, m, h->S, flags + n);
+                              (const double*)nullptr, m, h->S, flags.p + n);
     HIPCHK(hipGetLastError());
     std::vector<int32_t> fl((size_t)n + m + 1, 0), slot((size_t)n, -1);
-    HIPCHK(hipMemcpyAsync(fl.data(), flags, (size_t)(n + m) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(fl.data(), flags.p, (size_t)(n + m) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(slot.data(), h->nonant_slot, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipFree(flags));
+    flags.release();
     std::vector<int32_t> cmap((size_t)n, -1), rmap((size_t)m + 1, -1), pcol, prow;
     for (int j = 0; j < n; ++j)
         if (fl[j] || slot[j] >= 0) {
@@ -1928,9 +1953,8 @@ static int set_scenarios_shared(phgpu_state* h, const double* A_val, const doubl
         }
     h->np = (int)pcol.size();
     h->nr = (int)prow.size();
-    if (h->pcol) HIPCHK(hipFree(h->pcol));
-    if (h->prow) HIPCHK(hipFree(h->prow));
-    h->pcol = h->prow = nullptr;
+    dfree(h, &h->pcol);
+    dfree(h, &h->prow);
     if (dalloc(h, &h->pcol, pcol.size()) || dalloc(h, &h->prow, prow.size())) return -3;
     HIPCHK(hipMemcpy(h->cmap, cmap.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
     if (m) HIPCHK(hipMemcpy(h->rmap, rmap.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -1951,11 +1975,8 @@ static int set_scenarios_shared(phgpu_state* h, const double* A_val, const doubl
     h->sk_stride = o;
     const int64_t need = o * h->S;
     if (need > h->sk_cap) {
-        if (h->sk) {
-            HIPCHK(hipFree(h->sk));
-            h->ws_bytes -= h->sk_cap * (int64_t)sizeof(double);
-            h->sk = nullptr;
-        }
+        dfree(h, &h->sk);
+        h->sk_cap = 0;
         const int rc = dalloc(h, &h->sk, (size_t)need);
         if (rc) return rc;
         h->sk_cap = need;
@@ -2009,8 +2030,7 @@ extern "C" int phgpu_set_scenarios(phgpu_handle h, const double* A_val, const do
     HIPCHK(hipMemcpyAsync(h->node_of, node_of, (size_t)h->depth * Sz * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     h->xbar_mixed = -1;
     h->fx_valid = 0;
-    if (h->nb_idx) (void)hipFree(h->nb_idx);
-    h->nb_idx = nullptr;
+    dfree(h, &h->nb_idx);
     h->wslot = h->wq = 0;
     h->pending = -1;
     h->have_s[0] = h->have_s[1] = 0;
@@ -2096,6 +2116,8 @@ static int default_path(const phgpu_state* h) {
     return h->default_kernel;
 }
 
+#include "solve_launch.inc"
+
 static int solve_impl(phgpu_handle h, const phgpu_options* opt, int warm_start, int defer, double* x, double* y,
                       double* obj, double* bound, int32_t* status, int32_t* iters, void* stream) {
     if (!h) return set_err(-1, "null handle");
@@ -2107,7 +2129,6 @@ static int solve_impl(phgpu_handle h, const phgpu_options* opt, int warm_start, 
     h->pending = -1;
     h->wq = defer ? 1 - h->wslot : h->wslot;
     bind_slots(h);
-    const int wq = h->wq;
     phgpu_options o;
     if (opt) o = *opt;
     else phgpu_default_options(&o);
@@ -2117,24 +2138,7 @@ static int solve_impl(phgpu_handle h, const phgpu_options* opt, int warm_start, 
         return set_err(-1, "bad options (check_every=%d restart_every=%d max_iter=%d eta_frac=%g gamma=%g "
                        "eps_infeas=%g; check_every and max_iter must be multiples of restart_every)",
                        o.check_every, o.restart_every, o.max_iter, o.eta_frac, o.gamma, o.eps_infeas);
-    solve_params P;
-    P.eps_rel = o.eps_rel;
-    P.eps_abs = o.eps_abs;
-    P.gamma = o.gamma;
-    P.bsuff = o.beta_sufficient;
-    P.bnec = o.beta_necessary;
-    P.bart = o.beta_artificial > 0.0 ? o.beta_artificial : 1e300;
-    P.restart_every = o.restart_every;
-    P.eta_frac = o.eta_frac;
-    P.omega0 = o.omega0;
-    P.max_iter = o.max_iter;
-    P.check_every = o.check_every;
-    P.warm = (warm_start && h->have_solution) ? 1 : 0;
-    P.keep_omega = o.keep_omega;
-    P.infeas_start = o.infeas_start;
-    P.eps_inf = o.eps_infeas;
-    P.wmax = o.omega_clamp > 1.0 ? o.omega_clamp : 1e300;
-    P.wmin = 1.0 / P.wmax;
+    const solve_params P = make_solve_params(o, (warm_start && h->have_solution) ? 1 : 0);
     hipStream_t st = (hipStream_t)stream;
     // the register-resident kernels are specialised for the reflected step (gamma = 1, the
     // default); another gamma runs on the global-memory kernel
@@ -2144,101 +2148,10 @@ static int solve_impl(phgpu_handle h, const phgpu_options* opt, int warm_start, 
                        "other handles with paths 1-3, 5 and 6", o.kernel);
     if (h->shared) {
         if (!h->scen_set) return set_err(-1, "phgpu_set_scenarios has not been called");
-        int per_cu = 0;
-        // B scenario slots per workgroup (PHGPU_STREAM_SLOTS=1|2, default 2)
-        const char* env = getenv("PHGPU_STREAM_SLOTS");
-        const int B = (env && atoi(env) == 1) ? 1 : 2;
-        const void* fn = B == 1 ? (const void*)k_solve_stream<1> : (const void*)k_solve_stream<2>;
-        int& oc = h->occ_cache[B == 1 ? 4 : 5];
-        if (!oc) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&oc, fn, SBLK, 0));
-        per_cu = oc;
-        // PHGPU_STREAM_PER_CU=k: launch k workgroups per CU whatever the occupancy query says
-        // (the ones that do not fit wait for a free CU; the queue has no other dependency)
-        const char* pce = getenv("PHGPU_STREAM_PER_CU");
-        if (pce && atoi(pce) > 0) per_cu = std::min(atoi(pce), 8);
-        if (per_cu < 1) per_cu = 1;
-        int64_t nblk = (int64_t)per_cu * h->num_cus;
-        if (nblk > (h->S + B - 1) / B) nblk = (h->S + B - 1) / B;
-        // PHGPU_STREAM_SPLIT=T: the T longest scenarios of the previous solve run first, each
-        // over the whole GPU (the split form of k_solve_stream, cooperative launch), then the
-        // rest on the queue
-        const char* spe = getenv("PHGPU_STREAM_SPLIT");
-        int T = o.split_longest > 0 ? o.split_longest : (spe ? atoi(spe) : 0);
-        if (T < 0) T = 0;
-        if (T > 16) T = 16;
-        if (T > h->S) T = (int)h->S;
-        HIPCHK(hipMemsetAsync(h->qhead, 0, sizeof(int), st));
-        // queue order: longest first by the previous solve's iteration counts (the launch
-        // ends with its slowest scenario; starting it first shortens the tail)
-        if (!h->have_solution) HIPCHK(hipMemsetAsync(h->sk_iters, 0, (size_t)h->S * sizeof(int32_t), st));
-        if (h->S <= STREAM_ORDER_MAX)
-            hipLaunchKernelGGL(k_stream_order, dim3((unsigned)((h->S + 255) / 256)), dim3(256), 0, st, *h);
-        else
-            hipLaunchKernelGGL(k_stream_order_identity, dim3((unsigned)((h->S + 255) / 256)), dim3(256), 0, st, *h);
-        int occ = 0;
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)k_solve_stream<1, true>, SBLK, 0));
-        const int64_t cap = (int64_t)std::max(occ, 1) * h->num_cus;
-        // enough waves for one slice each in the longer pass: no more workgroups per scenario
-        const int kmax = std::max((std::max(h->nsl_c, h->nsl_r) + SWAVES - 1) / SWAVES, 1);
-        // the cluster form for a batch smaller than the GPU (a rank's share of a strong-
-        // scaling run): every scenario over K = capacity / S workgroups at once instead of
-        // one scenario per workgroup on a few CUs (PHGPU_STREAM_CLUSTER=0: off, =K: that K)
-        int Kc = 0;
-        {
-            const char* ce = getenv("PHGPU_STREAM_CLUSTER");
-            const int ask = ce ? atoi(ce) : -1;
-            if (ask != 0 && T == 0) {
-                int64_t k = cap / std::max<int64_t>(h->S, 1);
-                if (ask > 1) k = std::min<int64_t>(ask, k);
-                k = std::min<int64_t>(k, kmax);
-                if (k >= 2) Kc = (int)k;
-            }
-        }
-        if (T > 0 || Kc >= 2) {
-            // the split form: T stragglers over the whole grid (one cluster), or S clusters of Kc
-            const int ncl = Kc >= 2 ? (int)h->S : 1;
-            int G = Kc >= 2 ? (int)h->S * Kc : (int)std::min<int64_t>(kmax, cap);
-            G = std::max(G, 1);
-            const size_t need = (size_t)2 * G * 8 + (size_t)16 * ncl;  // partials, then 128-B barrier counters
-            if (h->split_need < need) {
-                if (h->split_part) HIPCHK(hipFree(h->split_part));
-                h->split_part = nullptr;
-                HIPCHK(hipMalloc((void**)&h->split_part, need * sizeof(double)));
-                h->split_need = need;
-            }
-            // the barrier counters start at gbase (PHGPU_SPLIT_BAR_BASE: a test starts them just
-            // below 2^32 so that they wrap during the launch; the barrier compares wrap-safe)
-            const char* bbe = getenv("PHGPU_SPLIT_BAR_BASE");
-            unsigned gbase = bbe ? (unsigned)strtoul(bbe, nullptr, 0) : 0u;
-            HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(h->split_part + (size_t)2 * G * 8), (int)gbase, (size_t)32 * ncl, st));
-            phgpu_state hv = *h;
-            int32_t* qh = h->qhead;
-            double* gp = h->split_part;
-            int q0 = Kc >= 2 ? (int)h->S : T;
-            int nc = ncl;
-            void* args[] = {&hv, &P, &qh, &x, &y, &obj, &bound, &status, &iters, &q0, &gp, &gbase, &nc};
-            HIPCHK(hipLaunchCooperativeKernel((const void*)k_solve_stream<1, true>, dim3((unsigned)G), dim3(SBLK), args,
-                                              0, st));
-            h->last_cluster = Kc >= 2 ? Kc : 0;
-        } else {
-            h->last_cluster = 0;
-        }
-        if (Kc < 2) {
-            nblk = std::min<int64_t>(nblk, std::max<int64_t>((h->S - T + B - 1) / B, 1));
-            if (B == 1)
-                hipLaunchKernelGGL(k_solve_stream<1>, dim3((unsigned)nblk), dim3(SBLK), 0, st, *h, P, h->qhead, x, y, obj,
-                                   bound, status, iters, T, (double*)nullptr, 0u, 1);
-            else
-                hipLaunchKernelGGL(k_solve_stream<2>, dim3((unsigned)nblk), dim3(SBLK), 0, st, *h, P, h->qhead, x, y, obj,
-                                   bound, status, iters, T, (double*)nullptr, 0u, 1);
-        }
-        HIPCHK(hipGetLastError());
+        const int rc4 = launch_stream(h, P, x, y, obj, bound, status, iters, st, o.split_longest);
+        if (rc4) return rc4;
         h->last_stats = nullptr;
-        h->last_status = status;
-        h->last_iters = iters;
-        h->have_s[wq] = 1;
-        h->last_path = 4;
-        bind_slots(h);
+        solve_done(h, 4, 0, 0, status, iters);
         return 0;
     }
     if (o.kernel == 2 && h->reg_inst < 0)
@@ -2304,163 +2217,21 @@ static int solve_impl(phgpu_handle h, const phgpu_options* opt, int warm_start, 
             if (frc) return frc;
         }
     }
-    const bool use_reg = path == 2;
-    int out_rec = 0;  // the warm state this solve writes lives in the records
-    if (path == 3 && !h->pk) {
-        const int rc3 = pack_alloc(h);
-        if (rc3) return rc3;
-        if (h->scen_set) HIPCHK(pack_fill(h, st));
+    int rc = 0;
+    if (path == 3) rc = launch_wg(h, P, x, y, obj, bound, status, iters, st);
+    else if (path == 2) rc = launch_reg(h, P, x, y, obj, bound, status, iters, st);
+    else {
+        rc = warm_from_records(h, P, st);
+        if (!rc && path == 5) rc = jit_prepare(h, st);
+        if (rc) return rc;
+        if (path == 5) rc = jit_launch(h, P, x, y, obj, bound, status, iters, st);
+        else if (path == 6) rc = ipm_launch(h, P, x, y, obj, bound, status, iters, st);
+        else rc = launch_global(h, P, x, y, obj, bound, status, iters, st);
     }
-    if (path == 3) {
-        // this solve's PH state into the records; a warm start left by another path too
-        HIPCHK(ph_to_records(h, st));
-        if (P.warm && !h->warm_rec) {
-            HIPCHK(to_records(h, h->x, h->n, h->pk_X, st));
-            HIPCHK(to_records(h, h->y, h->m, h->pk_Y, st));
-        }
-    }
-    if (path == 3) {
-        const wg_instance& gi = g_wg_instances[h->wg_inst];
-        wg_plan pl;
-        pl.L = WAVE * gi.WPS;
-        pl.kc = gi.KC;
-        pl.zc = gi.ZC;
-        pl.kr = gi.KR;
-        pl.zr = gi.ZR;
-        pl.col_id = h->wg_col_id;
-        pl.row_id = h->wg_row_id;
-        pl.col_long = h->wg_col_long;
-        pl.row_long = h->wg_row_long;
-        pl.col_k = h->wg_col_k;
-        pl.col_r = h->wg_col_r;
-        pl.row_k = h->wg_row_k;
-        pl.row_c = h->wg_row_c;
-        const size_t lds = wg_lds_doubles(h->n, h->m, gi.KC, gi.KR, gi.WPS) * sizeof(double);
-        int per_cu = 0;
-        int& oc = h->occ_cache[3];
-        if (!oc) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&oc, (const void*)gi.fn, pl.L, lds));
-        per_cu = oc;
-        if (per_cu < 1) per_cu = 1;
-        int64_t nblk = (int64_t)per_cu * h->num_cus;
-        if (nblk > h->S) nblk = h->S;
-        HIPCHK(hipMemsetAsync(h->qhead, 0, sizeof(int), st));
-        hipLaunchKernelGGL(gi.fn, dim3((unsigned)nblk), dim3(pl.L), lds, st, *h, P, pl, h->qhead, x, y, obj, bound,
-                           status, iters);
-        HIPCHK(hipGetLastError());
-        // outputs in the caller's scenario-fastest layout, unscaled
-        HIPCHK(from_records(h, h->pk_XW, h->pk_DC, h->n, x, st));
-        if (y) HIPCHK(from_records(h, h->pk_YW, h->pk_DR, h->m, y, st));
-        out_rec = 1;
-    } else if (use_reg) {
-        const int G = WAVE / h->reg_L;
-        const reg_instance& ri = g_reg_instances[h->reg_inst];
-        const size_t lds = (size_t)REG_WPB * reg_wave_lds(h->n, h->m, G, ri.KC, ri.KR) * sizeof(double);
-        // persistent grid: co-resident workgroups of REG_WPB independent waves (occupancy
-        // x CUs), never more than there are scenario groups
-        const int64_t need = (h->S + (int64_t)G * REG_WPB - 1) / ((int64_t)G * REG_WPB);
-        auto grid_of = [&](reg_kernel_t f, int& oc, int64_t& nb) -> hipError_t {
-            if (!oc) {
-                const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&oc, (const void*)f,
-                                                                                  WAVE * REG_WPB, lds);
-                if (e != hipSuccess) return e;
-            }
-            nb = (int64_t)(oc < 1 ? 1 : oc) * h->num_cus;
-            if (nb > need) nb = need;
-            return hipSuccess;
-        };
-        int64_t nblk = 0;
-        HIPCHK(grid_of(ri.fn, h->occ_cache[2], nblk));
-        // record mode (solve_reg.inc, template REC) when groups take more than one scenario
-        // each: then the queue order matters (PHGPU_REG_REC=0|1 pins it)
-        const char* env = getenv("PHGPU_REG_REC");
-        const bool rec = env ? atoi(env) != 0 : nblk * REG_WPB * G < h->S;
-        const reg_kernel_t fn = rec ? ri.fn_rec : ri.fn;
-        if (rec) HIPCHK(grid_of(ri.fn_rec, h->occ_cache[6], nblk));
-        const int64_t first_dyn = nblk * REG_WPB * G;
-        if (rec) {
-            if (!h->pk) {
-                const int rc3 = pack_alloc(h);
-                if (rc3) return rc3;
-                if (h->scen_set) HIPCHK(pack_fill(h, st));
-            }
-            if (P.warm && !h->warm_rec) {
-                HIPCHK(to_records(h, h->x, h->n, h->pk_X, st));
-                HIPCHK(to_records(h, h->y, h->m, h->pk_Y, st));
-            }
-            if (!h->have_solution) HIPCHK(hipMemsetAsync(h->sk_iters, 0, (size_t)h->S * sizeof(int32_t), st));
-            const dim3 ob((unsigned)((h->S + ORDER_BINS - 1) / ORDER_BINS));
-            int32_t* bins = h->sk_bins + 2 * ORDER_BINS * h->order_parity;
-            int32_t* other = h->sk_bins + 2 * ORDER_BINS * (1 - h->order_parity);
-            h->order_parity ^= 1;
-            // histogram + this solve's PH state into the records, one launch (k_reg_prep)
-            const bool ph = h->nn > 0 && (h->W_on || h->prox_on);
-            const int nh = (int)ob.x;
-            const int gx = (int)((h->S + TT - 1) / TT), gy = ph ? (3 * h->nn + TT - 1) / TT : 0;
-            hipLaunchKernelGGL(k_reg_prep, dim3((unsigned)(nh + gx * gy)), dim3(256), 0, st, h->sk_iters, h->S,
-                               P.restart_every, bins, nh, gx, h->W_on ? h->W : nullptr,
-                               h->prox_on ? h->rho : nullptr, h->prox_on ? h->xbar : nullptr, h->nn, h->pk,
-                               h->pk_stride, h->pk_W);
-            hipLaunchKernelGGL(k_reg_order, ob, dim3(ORDER_BINS), 0, st, h->sk_iters, h->S, P.restart_every, bins,
-                               other, h->sk_order, h->qhead);
-        } else if (P.warm && h->warm_rec) {
-            HIPCHK(from_records(h, h->pk_X, -1, h->n, h->x, st));
-            HIPCHK(from_records(h, h->pk_Y, -1, h->m, h->y, st));
-        }
-        reg_plan pl;
-        pl.L = h->reg_L;
-        pl.kc = h->reg_kc;
-        pl.zc = h->reg_zc;
-        pl.kr = h->reg_kr;
-        pl.zr = h->reg_zr;
-        pl.col_k = h->pl_col_k;
-        pl.col_r = h->pl_col_r;
-        pl.row_k = h->pl_row_k;
-        pl.row_c = h->pl_row_c;
-        pl.order = h->sk_order;
-        pl.last_iters = h->sk_iters;
-        pl.last_iters_w = h->its_w;
-        pl.ema = h->have_solution ? 1 : 0;
-        if (!rec) HIPCHK(hipMemsetAsync(h->qhead, 0, sizeof(int), st));  // record mode: k_reg_order did
-        hipLaunchKernelGGL(fn, dim3((unsigned)nblk), dim3(WAVE * REG_WPB), lds, st, *h, P, pl, h->qhead, first_dyn,
-                           x, y, obj, bound, status, iters);
-        HIPCHK(hipGetLastError());
-        if (rec) {
-            // outputs in the caller's scenario-fastest layout, unscaled
-            HIPCHK(from_records(h, h->pk_XW, h->pk_DC, h->n, x, st));
-            if (y) HIPCHK(from_records(h, h->pk_YW, h->pk_DR, h->m, y, st));
-        }
-        out_rec = rec ? 1 : 0;
-        h->last_rec = rec ? 1 : 0;
-    } else {
-        if (P.warm && h->warm_rec) {
-            HIPCHK(from_records(h, h->pk_X, -1, h->n, h->x, st));
-            HIPCHK(from_records(h, h->pk_Y, -1, h->m, h->y, st));
-        }
-        if (path == 5) {
-            const int rc5 = jit_prepare(h, st);
-            if (rc5) return rc5;
-            const int rc6 = jit_launch(h, P, x, y, obj, bound, status, iters, st);
-            if (rc6) return rc6;
-        } else if (path == 6) {
-            const int rc6 = ipm_launch(h, P, x, y, obj, bound, status, iters, st);
-            if (rc6) return rc6;
-        } else {
-            hipLaunchKernelGGL(k_solve, grid_for(h->S), dim3(BLOCK), 0, st, *h, P, x, y, obj, bound, status, iters);
-        }
-        out_rec = 0;
-    }
+    if (rc) return rc;
     HIPCHK(hipGetLastError());
-    h->last_status = status;
-    h->last_iters = iters;
-    if (path != 6) h->xp_C[wq] = 0;  // only path 6 writes x̄ partials with its outputs
-    // the warm state written by this solve; current now, or at phgpu_commit if deferred
-    h->have_s[wq] = 1;
-    h->warm_rec_s[wq] = out_rec;
-    h->last_path = path;
-    if (defer) h->pending = wq;
-    else h->wslot = wq;
-    h->wq = h->wslot;
-    bind_slots(h);
+    // the warm state this solve wrote lives in the records on path 3 and in path 2's record mode
+    solve_done(h, path, path == 3 || (path == 2 && h->last_rec == 1), defer, status, iters);
     return 0;
 }
 
@@ -2468,15 +2239,15 @@ static int solve_impl(phgpu_handle h, const phgpu_options* opt, int warm_start, 
 // node (xbar_single), and the node_buf index of each nonant for the folded PH step (nb_idx)
 static int xbar_layout(phgpu_state* h, hipStream_t st) {
     if (h->xbar_mixed >= 0) return 0;
-    int32_t* d = nullptr;
+    dev_tmp<int32_t> d;
     int32_t v[2] = {0, 0};
-    HIPCHK(hipMalloc((void**)&d, 2 * sizeof(int32_t)));
-    HIPCHK(hipMemsetAsync(d, 0, 2 * sizeof(int32_t), st));
-    hipLaunchKernelGGL(k_xbar_mixed, grid_for(h->S), dim3(BLOCK), 0, st, *h, d);
+    HIPCHK(d.alloc(2));
+    HIPCHK(hipMemsetAsync(d.p, 0, 2 * sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_xbar_mixed, grid_for(h->S), dim3(BLOCK), 0, st, *h, d.p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(v, d, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(v, d.p, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipFree(d));
+    d.release();
     h->xbar_mixed = v[0] ? 1 : 0;
     h->xbar_single = v[1] ? 0 : 1;
     if (h->xbar_single && h->nn > 0 && h->nn <= XL_NN_MAX && !h->nb_idx) {
@@ -2489,10 +2260,10 @@ static int xbar_layout(phgpu_state* h, hipStream_t st) {
             HIPCHK(hipMemcpy(&g, h->node_of + (size_t)dep[k] * h->S, sizeof(int32_t), hipMemcpyDeviceToHost));
             idx[k] = g * h->nlen_max + off[k];
         }
-        int32_t* di = nullptr;
-        HIPCHK(hipMalloc((void**)&di, h->nn * sizeof(int32_t)));
-        HIPCHK(hipMemcpy(di, idx.data(), h->nn * sizeof(int32_t), hipMemcpyHostToDevice));
-        h->nb_idx = di;
+        // (uncounted, as split_part, loop_dbl and loop_cnt: not part of phgpu_workspace_bytes)
+        const int rc = dalloc(h, &h->nb_idx, (size_t)h->nn, false);
+        if (rc) return rc;
+        HIPCHK(hipMemcpy(h->nb_idx, idx.data(), h->nn * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     return 0;
 }
@@ -2532,36 +2303,23 @@ extern "C" int phgpu_ph_loop(phgpu_handle h, const phgpu_options* opt, int max_i
     // buffers
     const int64_t nd = nblk * 16 + 16 + max_iters;
     if (h->loop_dbl_n < nd) {
-        if (h->loop_dbl) HIPCHK(hipFree(h->loop_dbl));
-        h->loop_dbl = nullptr;
-        HIPCHK(hipMalloc((void**)&h->loop_dbl, (size_t)nd * sizeof(double)));
+        dfree(h, &h->loop_dbl);
+        h->loop_dbl_n = 0;
+        const int rc = dalloc(h, &h->loop_dbl, (size_t)nd, false);
+        if (rc) return rc;
         h->loop_dbl_n = nd;
     }
-    if (!h->loop_cnt) HIPCHK(hipMalloc((void**)&h->loop_cnt, (size_t)(2 + PHGPU_STATS_WORDS) * sizeof(unsigned long long)));
+    if (!h->loop_cnt) {
+        const int rc = dalloc(h, &h->loop_cnt, (size_t)(2 + PHGPU_STATS_WORDS), false);
+        if (rc) return rc;
+    }
     HIPCHK(hipMemsetAsync(h->loop_cnt, 0, (size_t)(2 + PHGPU_STATS_WORDS) * sizeof(unsigned long long), st));
     // a plain (non-deferred) solve's slot bookkeeping (solve_impl)
     h->pending = -1;
     h->wq = h->wslot;
     bind_slots(h);
     const int wq = h->wq;
-    solve_params P;
-    P.eps_rel = o.eps_rel;
-    P.eps_abs = o.eps_abs;
-    P.gamma = o.gamma;
-    P.bsuff = o.beta_sufficient;
-    P.bnec = o.beta_necessary;
-    P.bart = o.beta_artificial > 0.0 ? o.beta_artificial : 1e300;
-    P.restart_every = o.restart_every;
-    P.eta_frac = o.eta_frac;
-    P.omega0 = o.omega0;
-    P.max_iter = o.max_iter;
-    P.check_every = o.check_every;
-    P.warm = h->have_solution ? 1 : 0;
-    P.keep_omega = o.keep_omega;
-    P.infeas_start = o.infeas_start;
-    P.eps_inf = o.eps_infeas;
-    P.wmax = o.omega_clamp > 1.0 ? o.omega_clamp : 1e300;
-    P.wmin = 1.0 / P.wmax;
+    const solve_params P = make_solve_params(o, h->have_solution ? 1 : 0);  // (options not validated here)
     const int par = h->ipm_parity;
     h->ipm_parity ^= 1;
     ipm_params a{};
@@ -2595,14 +2353,7 @@ extern "C" int phgpu_ph_loop(phgpu_handle h, const phgpu_options* opt, int max_i
         if (rc) return rc;
     }
     HIPCHK(hipGetLastError());
-    h->last_status = status;
-    h->last_iters = iters;
-    h->have_s[wq] = 1;
-    h->warm_rec_s[wq] = 0;
-    h->last_path = 6;
-    h->wslot = wq;
-    h->wq = h->wslot;
-    bind_slots(h);
+    solve_done(h, 6, 0, 0, status, iters);
     // the loop's record (one synchronisation: the loop is one call of the host's PH loop)
     std::vector<unsigned long long> cnt((size_t)(2 + PHGPU_STATS_WORDS));
     HIPCHK(hipMemcpyAsync(cnt.data(), h->loop_cnt, cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
@@ -2753,10 +2504,7 @@ static int two_stage_only(phgpu_state* h, const char* who) {
 static int ws_alloc(phgpu_state* h, ph_ws& w, size_t npart, size_t ntag) {
     int rc = dalloc(h, &w.part, npart);
     if (!rc) rc = dalloc(h, &w.tag, ntag);
-    if (rc && w.part) {
-        (void)hipFree(w.part);
-        w.part = nullptr;
-    }
+    if (rc) dfree(h, &w.part);
     return rc;
 }
 static int wave_ws(phgpu_state* h, ph_ws& w, int nv) {
@@ -3146,64 +2894,12 @@ extern "C" int phgpu_fixer_step(phgpu_handle h, const phgpu_fixer_params* prm, c
 extern "C" int phgpu_destroy(phgpu_handle h) {
     if (!h) return 0;
     rccl_release(h);
-    g_ipm_tuning_of.erase(h);
-    h->pend.active = 0;  // a deferred step that never ran is dropped with the handle
-    if (h->oms[0]) {  // the x / y / omega / sk_iters fields may be bound to slot 1: free by slot
-        h->x = h->xs[0];
-        h->y = h->ys[0];
-        h->omega = h->oms[0];
-        h->sk_iters = h->its_s[0];
-    }
-    void* ptrs[] = {h->row_ptr, h->col_idx, h->col_ptr, h->row_idx, h->perm, h->row_of,
-                    h->nonant_col, h->nonant_depth, h->nonant_off, h->nonant_slot,
-                    h->A, h->c, h->lb, h->ub, h->q, h->rl, h->ru, h->objc, h->prob, h->pcoef,
-                    h->node_of, h->Ah_csr, h->Ah_csc, h->Dr, h->Dc, h->normA, h->lbh, h->ubh,
-                    h->rlh, h->ruh, h->ch, h->qh, h->x, h->x0, h->xe, h->xt, h->aty, h->aty0,
-                    h->y, h->y0, h->yt, h->omega, h->part, h->part_node, h->pl_col_k,
-                    h->pl_col_r, h->pl_row_k, h->pl_row_c, h->qhead, h->wg_col_id, h->wg_row_id,
-                    h->wg_col_long, h->wg_row_long, h->wg_col_k, h->wg_col_r, h->wg_row_k, h->wg_row_c,
-                    h->pk, h->cmap, h->rmap, h->pcol, h->prow, h->sh_col, h->sh_row, h->sh_norm, h->sh_v,
-                    h->sh_u, h->sh_w, h->sh_part, h->sk, h->cs_off, h->cs_len, h->cs_idx, h->cs_src,
-                    h->rs_off, h->rs_len, h->rs_idx, h->rs_src, h->cs_val, h->rs_val, h->sk_iters, h->sk_order,
-                    h->sk_bins, h->cw_ptr, h->cw_slc, h->rw_ptr, h->rw_slc};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (h->split_part) (void)hipFree(h->split_part);
-    if (h->jit) {
-        if (h->jit->mod) (void)hipModuleUnload(h->jit->mod);
-        delete h->jit;
-    }
-    if (h->ipm) {
-        if (h->ipm->mod) (void)hipModuleUnload(h->ipm->mod);
-        delete h->ipm;
-    }
-    if (h->ipm_loop) {
-        if (h->ipm_loop->mod) (void)hipModuleUnload(h->ipm_loop->mod);
-        delete h->ipm_loop;
-    }
-    if (h->loop_dbl) (void)hipFree(h->loop_dbl);
-    if (h->loop_cnt) (void)hipFree(h->loop_cnt);
-    if (h->ipm_list) (void)hipFree(h->ipm_list);
-    if (h->ipm_cnt) (void)hipFree(h->ipm_cnt);
-    if (h->ipm_stats) (void)hipFree(h->ipm_stats);
-    if (h->ipm_prof) (void)hipFree(h->ipm_prof);
-    if (h->stats_gen) (void)hipFree(h->stats_gen);
-    {
-        void* more[] = {h->xp[0], h->xp[1], h->xp_node[0], h->xp_node[1], h->xp_dirty[0], h->xp_dirty[1],
-                        h->cpart_blk, h->blk_cnt, h->nb_idx, h->fx_nloc};
-        for (void* p : more)
-            if (p) (void)hipFree(p);
-        for (const ph_ws& w : {h->rs, h->ns, h->nc, h->wd, h->rr}) {
-            if (w.part) (void)hipFree(w.part);
-            if (w.tag) (void)hipFree(w.tag);
-        }
-    }
-    if (!h->shared) {  // warm-start slot 1 (slot 0 is x / y / omega / sk_iters above)
-        void* slot1[] = {h->xs[1], h->ys[1], h->oms[1], h->its_s[1]};
-        for (void* p : slot1)
-            if (p) (void)hipFree(p);
-    }
-    delete h;
+    module_release(h->jit);
+    module_release(h->ipm);
+    module_release(h->ipm_loop);
+    phgpu_owner* o = owner_of(h);  // (a deferred step that never ran is dropped with it)
+    for (const dev_alloc& a : o->allocs) (void)hipFree(a.p);
+    delete o;
     return 0;
 }
 

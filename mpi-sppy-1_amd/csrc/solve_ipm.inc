@@ -1048,10 +1048,6 @@ static int ipm_lanes(const phgpu_state* h) {
     return 1;
 }
 
-// flags (one synchronisation), then the cached module or a new one
-// phgpu_set_ipm_tuning's definitions, by handle (host side: the state is a kernel argument)
-static std::map<const phgpu_state*, std::string> g_ipm_tuning_of;
-
 // Compile a path-6 source and load it: the IPM kernel `fname` (L lanes / threads per
 // scenario) with its occupancy and resources and, when want_pdhg, the module's path-5 kernel
 // (the fallback).  *out is the new module (key = src); mr / nf / flops are the caller's.
@@ -1076,41 +1072,35 @@ static int ipm_module_load(const std::string& src, int L, const char* fname, boo
     if (e == hipSuccess) e = hipFuncGetAttribute(&im->private_bytes, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, im->fn_ipm);
     if (e == hipSuccess) e = hipFuncGetAttribute(&im->vgprs, HIP_FUNC_ATTRIBUTE_NUM_REGS, im->fn_ipm);
     if (e != hipSuccess) {
-        if (im->mod) (void)hipModuleUnload(im->mod);
-        delete im;
+        module_release(im);
         return set_err(-2, "loading the %s module failed: %s", what, hipGetErrorString(e));
     }
     *out = im;
     return 0;
 }
 
+// flags (one synchronisation), then the cached module or a new one
 static int ipm_prepare(phgpu_state* h, hipStream_t st) {
     if (h->ipm && h->ipm_flags_valid && h->ipm->L == ipm_lanes(h)) return 0;
-    struct tuning_scope {
-        explicit tuning_scope(const phgpu_state* hh) {
-            auto it = g_ipm_tuning_of.find(hh);
-            g_ipm_tuning = it != g_ipm_tuning_of.end() ? &it->second : nullptr;
+    struct tuning_scope {  // the handle's phgpu_set_ipm_tuning definitions, for ipm_source
+        explicit tuning_scope(phgpu_state* hh) {
+            const std::string& t = owner_of(hh)->ipm_tuning;
+            g_ipm_tuning = t.empty() ? nullptr : &t;
         }
         ~tuning_scope() { g_ipm_tuning = nullptr; }
     } tuning(h);
     const int n = h->n, m = h->m, nnz = h->nnz;
     const int E = nnz + 4 * n + 2 * m;
     // temporary device buffers of the flag pass, freed on every exit path
-    struct dev_tmp {
-        int32_t* df = nullptr;
-        double* dv = nullptr;
-        ~dev_tmp() {
-            if (df) (void)hipFree(df);
-            if (dv) (void)hipFree(dv);
-        }
-    } tmp;
-    HIPCHK(hipMalloc((void**)&tmp.df, (size_t)E * sizeof(int32_t)));
-    HIPCHK(hipMalloc((void**)&tmp.dv, (size_t)E * sizeof(double)));
-    hipLaunchKernelGGL(k_ipm_flags, dim3((unsigned)E), dim3(256), 0, st, *h, tmp.df, tmp.dv);
+    dev_tmp<int32_t> df;
+    dev_tmp<double> dv;
+    HIPCHK(df.alloc((size_t)E));
+    HIPCHK(dv.alloc((size_t)E));
+    hipLaunchKernelGGL(k_ipm_flags, dim3((unsigned)E), dim3(256), 0, st, *h, df.p, dv.p);
     std::vector<int32_t> flags((size_t)E), slot((size_t)n), rp((size_t)m + 1), ci((size_t)std::max(nnz, 1));
     std::vector<double> v0((size_t)E);
-    HIPCHK(hipMemcpyAsync(flags.data(), tmp.df, (size_t)E * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(v0.data(), tmp.dv, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(flags.data(), df.p, (size_t)E * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(v0.data(), dv.p, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(slot.data(), h->nonant_slot, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(rp.data(), h->row_ptr, (size_t)(m + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (nnz) HIPCHK(hipMemcpyAsync(ci.data(), h->col_idx, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -1141,10 +1131,7 @@ static int ipm_prepare(phgpu_state* h, hipStream_t st) {
     im->nf = inf[1];
     im->fac_flops = inf[2];
     im->sol_flops = inf[3];
-    if (h->ipm) {
-        (void)hipModuleUnload(h->ipm->mod);
-        delete h->ipm;
-    }
+    module_release(h->ipm);
     h->ipm = im;
     h->ipm_flags_valid = 1;
     // a one-lane kernel that spills: its slack reciprocals (2 (n + m) doubles per lane, written
@@ -1335,10 +1322,7 @@ static int ipm_loop_prepare(phgpu_state* h) {
     im->nf = h->ipm->nf;
     im->fac_flops = h->ipm->fac_flops;
     im->sol_flops = h->ipm->sol_flops;
-    if (h->ipm_loop) {
-        (void)hipModuleUnload(h->ipm_loop->mod);
-        delete h->ipm_loop;
-    }
+    module_release(h->ipm_loop);
     h->ipm_loop = im;
     return 0;
 }
@@ -1373,7 +1357,6 @@ extern "C" int phgpu_set_ipm_tuning(phgpu_handle h, const char* defs) {
         norm += p.first + "=" + p.second + ";";
     }
     if (h->ipm) return set_err(-1, "phgpu_set_ipm_tuning: the interior-point module is already built (call it before the first solve)");
-    if (norm.empty()) g_ipm_tuning_of.erase(h);
-    else g_ipm_tuning_of[h] = norm;
+    owner_of(h)->ipm_tuning = norm;
     return 0;
 }

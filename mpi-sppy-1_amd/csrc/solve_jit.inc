@@ -177,18 +177,18 @@ static int jit_compile(const std::string& src, std::vector<char>& code, bool max
 static int jit_prepare(phgpu_state* h, hipStream_t st) {
     const int n = h->n, m = h->m;
     if (h->jit && h->jit_kinds_valid) return 0;
-    int32_t* dk = nullptr;
-    HIPCHK(hipMalloc((void**)&dk, (size_t)(n + m) * sizeof(int32_t)));
-    HIPCHK(hipMemsetAsync(dk, 0, (size_t)(n + m) * sizeof(int32_t), st));
-    hipLaunchKernelGGL(k_jit_kinds, dim3((unsigned)(n + m)), dim3(256), 0, st, *h, dk);
+    dev_tmp<int32_t> dk;
+    HIPCHK(dk.alloc((size_t)(n + m)));
+    HIPCHK(hipMemsetAsync(dk.p, 0, (size_t)(n + m) * sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_jit_kinds, dim3((unsigned)(n + m)), dim3(256), 0, st, *h, dk.p);
     std::vector<int32_t> kinds((size_t)(n + m)), slot((size_t)n), rp((size_t)m + 1), ci((size_t)std::max(h->nnz, 1));
-    HIPCHK(hipMemcpyAsync(kinds.data(), dk, (size_t)(n + m) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(kinds.data(), dk.p, (size_t)(n + m) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(slot.data(), h->nonant_slot, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(rp.data(), h->row_ptr, (size_t)(m + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (h->nnz)
         HIPCHK(hipMemcpyAsync(ci.data(), h->col_idx, (size_t)h->nnz * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipFree(dk));
+    dk.release();
     const char* env = getenv("PHGPU_JIT_WPE");
     const int wpe = (env && atoi(env) >= 1 && atoi(env) <= 8) ? atoi(env) : 1;
     const std::string pre = jit_preamble(n, m, h->nnz, rp, ci, slot, kinds, wpe);
@@ -208,14 +208,10 @@ static int jit_prepare(phgpu_state* h, hipStream_t st) {
     if (e == hipSuccess) e = hipModuleGetFunction(&jm->fn, jm->mod, "k_solve_jit");
     if (e == hipSuccess) e = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&jm->per_cu, jm->fn, 256, 0);
     if (e != hipSuccess) {
-        if (jm->mod) (void)hipModuleUnload(jm->mod);
-        delete jm;
+        module_release(jm);
         return set_err(-2, "loading the path-5 kernel failed: %s", hipGetErrorString(e));
     }
-    if (h->jit) {
-        (void)hipModuleUnload(h->jit->mod);
-        delete h->jit;
-    }
+    module_release(h->jit);
     h->jit = jm;
     h->jit_kinds_valid = 1;
     return 0;

@@ -16,6 +16,8 @@
  *                                          mpisppy/spopt.py:310-439 -> phgpu_expectations
  *   - Fixer.miditer (counters, decisions, var.fix)
  *                                          mpisppy/extensions/fixer.py:114-304 -> phgpu_fixer_step
+ *   - FWPH's column set and QP per scenario (SDM, _add_QP_column, _conv_diff)
+ *                                          mpisppy/fwph/fwph.py:210-370, 528-547 -> phgpu_fwph_*
  *
  * The cross-rank sums (the per-node MPI Allreduce of phbase.py:83-87 and the
  * ROOT-comm Allreduce of phbase.py:341) are done by the caller (RCCL all-reduce of
@@ -509,6 +511,82 @@ typedef struct {
 int phgpu_fixer_step(phgpu_handle h, const phgpu_fixer_params* prm, const double* node_buf,
                      const double* th, const int32_t* nb, const int32_t* lb, const int32_t* ub,
                      int32_t* count, double* fixval, int32_t* nfix, int64_t* totals, void* stream);
+
+/* FWPH (mpisppy/fwph/fwph.py), the half of Boland et al.'s Algorithm 2 that is not an LP solve:
+ * per local scenario a set of columns X_j in R^nn (the nonant values of LP solutions, the layout
+ * of W) with costs f_j = c.x + obj_const, weights a on the simplex, the QP point xq = sum a_j X_j
+ * and phi = sum a_j f_j.  The reference keeps them in a second Pyomo model per scenario
+ * (_initialize_QP_subproblems, fwph.py:685-771) and calls a QP solver per scenario and inner
+ * iteration (:284-289); here one pass serves all local scenarios.  All entries are ordered on
+ * the stream and never synchronise (phgpu_fwph_init does when it resizes an existing store), work
+ * on a PHGPU_SHARED_MATRIX handle, for any nn and any tree, and give the same bits on every run.
+ *
+ * phgpu_fwph_init: allocate the store for max_cols columns per scenario (2 <= max_cols <= 64) and
+ * empty it.  The store is the handle's: counted in phgpu_workspace_bytes from this call on,
+ * freed by phgpu_destroy (or by an init with another max_cols).  Scenario-fastest; per scenario
+ * max_cols (nn + 5) + max_cols (max_cols + 1) + nn + 1 doubles (columns, costs, weights, three
+ * work vectors, the rho-weighted Gram matrix of the columns and its Cholesky work space, xq, phi)
+ * and four int32 (columns held, active flag, newest column, inner iterations so far). */
+int phgpu_fwph_init(phgpu_handle h, int32_t max_cols, void* stream);
+
+/* Fill the store of every local scenario with K columns (_initialize_QP_var_values,
+ * fwph.py:773-791: K = 1, Iter0's solution; the initial points of :744-755).
+ *   X: device [K][nn][S], f: device [K][S], a: device [K][S] or NULL (a = e_0);
+ *   rho: device [nn*S], the rho of every later call (the Gram matrix is kept up to date as
+ *   columns arrive and never recomputed: rho must not change while the store is in use);
+ *   xq: device [nn*S] or NULL and xqx: device [n*S] or NULL receive the QP point (xqx in its
+ *   nonant columns only).  Every scenario becomes active with 0 inner iterations. */
+int phgpu_fwph_load(phgpu_handle h, int32_t K, const double* X, const double* f, const double* a,
+                    const double* rho, double* xq, double* xqx, void* stream);
+
+/* Copy the store out (tests, _gather_weight_dict-style reporting); every pointer may be NULL.
+ *   X: [max_cols][nn][S], f, a: [max_cols][S] (0 beyond a scenario's columns), ncols [S],
+ *   xq [nn*S], phi [S], active [S], nit [S] (columns added since the load, replaced ones too). */
+int phgpu_fwph_export(phgpu_handle h, double* X, double* f, double* a, int32_t* ncols, double* xq,
+                      double* phi, int32_t* active, int32_t* nit, void* stream);
+
+/* The LP's dual weights of one inner iteration (SDM, fwph.py:227-247), for every scenario:
+ *   What = W + rho (src - xbar),  src = (1 - alpha) xbar + alpha xq if t0, else xq
+ * What: device [nn*S], what phgpu_set_ph_state binds as W for the LP solve.  With t0 (the first
+ * inner iteration of an outer one) every scenario is marked active. */
+int phgpu_fwph_direction(phgpu_handle h, int t0, double alpha, const double* W, const double* rho,
+                         const double* xbar, double* What, void* stream);
+
+typedef struct {
+    double conv_thresh;     /* FW_conv_thresh: a scenario with Gamma < this is done (fwph.py:291) */
+    double stop_check_tol;  /* stop_check_tol: Gamma < -this is counted (the warning of :275-278) */
+} phgpu_fwph_params;
+
+/* One inner iteration of SDM after the LP solve (fwph.py:256-292, _add_QP_column :305-370), one
+ * pass over the local scenarios.  x, obj, bound, status: the outputs of the solve with What
+ * bound as W, W on and prox off.  For every active scenario whose status is OPTIMAL:
+ *   val0 = obj, val1 = phi + What.xq (the QP point before this pass),
+ *   Gamma = (val1 - val0) / |val0| if |val0| > 1e-9 else val1 - val0;
+ *   the column (x's nonants, obj - What.x) is appended; a scenario that holds max_cols columns
+ *   overwrites the one with the smallest weight, ties to the lowest index, never the newest
+ *   (THIS DEPARTS FROM fwph.py, which never drops a column);
+ *   min_a sum a_j f_j + W.x(a) + sum_k rho_k / 2 (x(a)_k - xbar_k)^2 on the simplex (W, not What)
+ *   is solved by an active set on the Gram matrix (exact up to rounding; a is not unique, x(a)
+ *   and phi are), from a cold start, so xq and phi depend on the columns only;
+ *   the scenario stays active iff !(Gamma < conv_thresh) -- tested after the column and the QP.
+ * An active scenario whose status is not OPTIMAL adds nothing, keeps its QP point and becomes
+ * inactive (THIS DEPARTS FROM fwph.py:510-517, which raises).  Inactive scenarios are untouched.
+ *   gamma [S], ncols [S], xq [nn*S], xqx [n*S] (nonant columns): written for the scenarios that
+ *   added a column;  dual_bound [S]: = bound, written only with t0, for every active scenario;
+ *   counts: int32[4], device or host-mapped pinned memory, written last by one 16-byte store:
+ *   {scenarios still active, scenarios with Gamma < -stop_check_tol, active scenarios whose LP
+ *   was not OPTIMAL, 0} of this pass. */
+int phgpu_fwph_column(phgpu_handle h, const phgpu_fwph_params* prm, int t0, const double* x,
+                      const double* obj, const double* bound, const int32_t* status, const double* W,
+                      const double* What, const double* rho, const double* xbar, double* gamma,
+                      double* dual_bound, int32_t* ncols, double* xq, double* xqx, int32_t* counts,
+                      void* stream);
+
+/* _conv_diff (fwph.py:528-547) without its Allreduce: out[0] = sum_s prob_s sum_k (xq - xbar)^2
+ * over the local scenarios (xbar: device [nn*S], the OLD x̄).  Per-thread sums in index order,
+ * per-block sums in a fixed order, the blocks' sums by a fixed tree in the block with the last
+ * ticket (as phgpu_w_diff).  out: device double[1]. */
+int phgpu_fwph_diff(phgpu_handle h, const double* xbar, double* out, void* stream);
 
 /* Free the workspace and the handle. */
 int phgpu_destroy(phgpu_handle h);

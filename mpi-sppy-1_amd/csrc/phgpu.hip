@@ -68,6 +68,7 @@ static int set_err(int code, const char* fmt, ...) {
 // ------------------------------------------------------------------ state
 struct jit_module;  // solve_jit.inc: the hipRTC-compiled path-5 kernel of a handle
 struct ipm_module;  // solve_ipm.inc: the hipRTC-compiled path-6 module of a handle
+struct fwph_store;  // ph_fwph.inc: the FWPH column store of a handle
 struct ph_ws {      // a reduction's device workspace: partials, and node tags or a ticket counter
     double* part;
     int32_t* tag;
@@ -246,6 +247,10 @@ struct phgpu_state {
     // first call; the former counted again after new scenario data (fx_valid 0)
     int32_t* fx_nloc;
     int fx_valid;
+    // phgpu_fwph_*: the column store (host record of its device buffers; null until
+    // phgpu_fwph_init) and the per-block partials and ticket of phgpu_fwph_diff
+    fwph_store* fw;
+    ph_ws fwd;
 };
 
 // ------------------------------------------------------------------ ownership (host)
@@ -1101,6 +1106,7 @@ __global__ void k_stats_copy(const unsigned long long* __restrict__ src, int cop
 // (kernels and device helpers; their entry points are under "C-ABI" below)
 #include "ph_reduce.inc"
 #include "ph_fixer.inc"
+#include "ph_fwph.inc"
 
 // Xhat_Eval._fix_nonants (utils/xhat_eval.py; spopt.py _fix_nonants): nonant columns of
 // every scenario get lb = ub = xfix[k, s] (scaled); xfix == NULL restores the model bounds.
@@ -2889,6 +2895,150 @@ extern "C" int phgpu_fixer_step(phgpu_handle h, const phgpu_fixer_params* prm, c
     return 0;
 }
 
+// ------------------------------------------------------------------ FWPH (ph_fwph.inc)
+static void fwph_release(phgpu_state* h) {
+    fwph_store* fw = h->fw;
+    if (!fw) return;
+    dfree(h, &fw->X);
+    dfree(h, &fw->f);
+    dfree(h, &fw->a);
+    dfree(h, &fw->G);
+    dfree(h, &fw->L);
+    dfree(h, &fw->lin);
+    dfree(h, &fw->u);
+    dfree(h, &fw->v);
+    dfree(h, &fw->xq);
+    dfree(h, &fw->phi);
+    dfree(h, &fw->ncols);
+    dfree(h, &fw->active);
+    dfree(h, &fw->last);
+    dfree(h, &fw->nit);
+    dfree(h, &fw->acc);
+    delete fw;
+    h->fw = nullptr;
+}
+
+// fwph.py:685-771 (_initialize_QP_subproblems): one store for all local scenarios
+extern "C" int phgpu_fwph_init(phgpu_handle h, int32_t max_cols, void* stream) {
+    if (!h) return set_err(-1, "null handle");
+    if (max_cols < 2 || max_cols > 64) return set_err(-1, "phgpu_fwph_init: max_cols %d is not in [2, 64]", max_cols);
+    if (!h->scen_set) return set_err(-1, "phgpu_fwph_init: no scenario data yet");
+    FLUSH_STEP(h);
+    hipStream_t st = (hipStream_t)stream;
+    if (h->fw && h->fw->max_cols != max_cols) {
+        HIPCHK(hipStreamSynchronize(st));  // (a resize: nothing of the old store may be in flight)
+        fwph_release(h);
+    }
+    const size_t S = (size_t)h->S, nn = (size_t)std::max(1, h->nn), K = (size_t)max_cols, T = K * (K + 1) / 2;
+    if (!h->fw) {
+        fwph_store* fw = new (std::nothrow) fwph_store();
+        if (!fw) return set_err(-3, "out of host memory");
+        memset(fw, 0, sizeof(*fw));
+        fw->max_cols = max_cols;
+        h->fw = fw;
+        int rc = dalloc(h, &fw->X, K * nn * S);
+        if (!rc) rc = dalloc(h, &fw->f, K * S);
+        if (!rc) rc = dalloc(h, &fw->a, K * S);
+        if (!rc) rc = dalloc(h, &fw->G, T * S);
+        if (!rc) rc = dalloc(h, &fw->L, T * S);
+        if (!rc) rc = dalloc(h, &fw->lin, K * S);
+        if (!rc) rc = dalloc(h, &fw->u, K * S);
+        if (!rc) rc = dalloc(h, &fw->v, K * S);
+        if (!rc) rc = dalloc(h, &fw->xq, nn * S);
+        if (!rc) rc = dalloc(h, &fw->phi, S);
+        if (!rc) rc = dalloc(h, &fw->ncols, S);
+        if (!rc) rc = dalloc(h, &fw->active, S);
+        if (!rc) rc = dalloc(h, &fw->last, S);
+        if (!rc) rc = dalloc(h, &fw->nit, S);
+        if (!rc) rc = dalloc(h, &fw->acc, (size_t)4);
+        if (rc) {
+            fwph_release(h);
+            return rc;
+        }
+    }
+    fwph_store* fw = h->fw;
+    HIPCHK(hipMemsetAsync(fw->xq, 0, nn * S * sizeof(double), st));
+    HIPCHK(hipMemsetAsync(fw->phi, 0, S * sizeof(double), st));
+    HIPCHK(hipMemsetAsync(fw->ncols, 0, S * sizeof(int32_t), st));
+    HIPCHK(hipMemsetAsync(fw->active, 0, S * sizeof(int32_t), st));
+    HIPCHK(hipMemsetAsync(fw->last, 0, S * sizeof(int32_t), st));
+    HIPCHK(hipMemsetAsync(fw->nit, 0, S * sizeof(int32_t), st));
+    HIPCHK(hipMemsetAsync(fw->acc, 0, 4 * sizeof(int32_t), st));
+    return 0;
+}
+
+#define FWPH_READY(h, who)                                                        \
+    do {                                                                          \
+        if (!(h)) return set_err(-1, "null handle");                              \
+        if (!(h)->fw) return set_err(-1, who ": phgpu_fwph_init has not run");   \
+        FLUSH_STEP(h);                                                            \
+    } while (0)
+
+// fwph.py:773-791 (_initialize_QP_var_values) and the initial points of :744-755
+extern "C" int phgpu_fwph_load(phgpu_handle h, int32_t K, const double* X, const double* f, const double* a,
+                               const double* rho, double* xq, double* xqx, void* stream) {
+    FWPH_READY(h, "phgpu_fwph_load");
+    if (!X || !f || !rho) return set_err(-1, "null argument");
+    if (K < 1 || K > h->fw->max_cols) return set_err(-1, "phgpu_fwph_load: %d columns, the store holds 1..%d", K, h->fw->max_cols);
+    hipLaunchKernelGGL(k_fw_load, dim3((unsigned)((h->S + FW_T - 1) / FW_T)), dim3(FW_T), 0, (hipStream_t)stream, *h,
+                       *h->fw, (int)K, X, f, a, rho, xq, xqx);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int phgpu_fwph_export(phgpu_handle h, double* X, double* f, double* a, int32_t* ncols, double* xq,
+                                 double* phi, int32_t* active, int32_t* nit, void* stream) {
+    FWPH_READY(h, "phgpu_fwph_export");
+    hipLaunchKernelGGL(k_fw_export, dim3((unsigned)((h->S + FW_T - 1) / FW_T)), dim3(FW_T), 0, (hipStream_t)stream,
+                       *h, *h->fw, X, f, a, ncols, xq, phi, active, nit);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// fwph.py:227-247
+extern "C" int phgpu_fwph_direction(phgpu_handle h, int t0, double alpha, const double* W, const double* rho,
+                                    const double* xbar, double* What, void* stream) {
+    FWPH_READY(h, "phgpu_fwph_direction");
+    if (!W || !rho || !xbar || !What) return set_err(-1, "null argument");
+    if (h->nn == 0) return 0;
+    const int64_t bx = std::min<int64_t>((h->S + GR_T - 1) / GR_T, std::max<int64_t>(1, UPD_BLOCKS / std::max(1, h->nn)));
+    hipLaunchKernelGGL(k_fw_direction, dim3((unsigned)bx, (unsigned)std::min(h->nn, GR_ROWS)), dim3(GR_T), 0,
+                       (hipStream_t)stream, *h, *h->fw, t0 ? 1 : 0, alpha, W, rho, xbar, What);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// fwph.py:256-292 and 305-370 (_add_QP_column)
+extern "C" int phgpu_fwph_column(phgpu_handle h, const phgpu_fwph_params* prm, int t0, const double* x,
+                                 const double* obj, const double* bound, const int32_t* status, const double* W,
+                                 const double* What, const double* rho, const double* xbar, double* gamma,
+                                 double* dual_bound, int32_t* ncols, double* xq, double* xqx, int32_t* counts,
+                                 void* stream) {
+    FWPH_READY(h, "phgpu_fwph_column");
+    if (!prm || !x || !obj || !bound || !status || !W || !What || !rho || !xbar || !gamma || !dual_bound || !ncols ||
+        !xq || !xqx || !counts)
+        return set_err(-1, "null argument");
+    hipLaunchKernelGGL(k_fw_column, dim3((unsigned)((h->S + FW_T - 1) / FW_T)), dim3(FW_T), 0, (hipStream_t)stream, *h,
+                       *h->fw, *prm, t0 ? 1 : 0, x, obj, bound, status, W, What, rho, xbar, gamma, dual_bound, ncols, xq,
+                       xqx, counts);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// fwph.py:528-547 (_conv_diff)
+extern "C" int phgpu_fwph_diff(phgpu_handle h, const double* xbar, double* out, void* stream) {
+    FWPH_READY(h, "phgpu_fwph_diff");
+    if (!xbar || !out) return set_err(-1, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = ticket_ws(h, h->fwd, WD_BLOCKS, st);
+    if (rc) return rc;
+    const int64_t nblk = std::max<int64_t>(1, std::min<int64_t>((h->S + GR_T - 1) / GR_T, WD_BLOCKS));
+    hipLaunchKernelGGL(k_fw_diff, dim3((unsigned)nblk), dim3(GR_T), 0, st, *h, *h->fw, xbar, h->fwd.part, h->fwd.tag,
+                       out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 #include "comm_rccl.inc"
 
 extern "C" int phgpu_destroy(phgpu_handle h) {
@@ -2897,6 +3047,7 @@ extern "C" int phgpu_destroy(phgpu_handle h) {
     module_release(h->jit);
     module_release(h->ipm);
     module_release(h->ipm_loop);
+    delete h->fw;  // (its device buffers are in allocs)
     phgpu_owner* o = owner_of(h);  // (a deferred step that never ran is dropped with it)
     for (const dev_alloc& a : o->allocs) (void)hipFree(a.p);
     delete o;

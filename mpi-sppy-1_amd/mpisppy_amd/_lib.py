@@ -60,6 +60,14 @@ class FixerParams(ctypes.Structure):
     ]
 
 
+class FwphParams(ctypes.Structure):
+    """phgpu_fwph_params (include/phgpu.h): the thresholds of FWPH's column pass."""
+    _fields_ = [
+        ("conv_thresh", c_dbl),
+        ("stop_check_tol", c_dbl),
+    ]
+
+
 OPTIMAL, ITER_LIMIT, PRIMAL_INFEASIBLE, DUAL_INFEASIBLE = 0, 1, 2, 3
 SHARED_MATRIX = 1          # phgpu_create2 flag (include/phgpu.h)
 
@@ -74,7 +82,9 @@ EXPORTS = ["phgpu_default_options", "phgpu_create", "phgpu_create2", "phgpu_set_
            "phgpu_ph_loop", "phgpu_stream_info", "phgpu_comm_unique_id", "phgpu_comm_init",
            "phgpu_allreduce_sum", "phgpu_ph_residuals", "phgpu_norm_rho_update",
            "phgpu_nonant_stats", "phgpu_nonant_closest", "phgpu_grad_cost", "phgpu_w_diff",
-           "phgpu_rho_ratio_stats", "phgpu_rho_from_stats", "phgpu_fixer_step"]
+           "phgpu_rho_ratio_stats", "phgpu_rho_from_stats", "phgpu_fixer_step",
+           "phgpu_fwph_init", "phgpu_fwph_load", "phgpu_fwph_export", "phgpu_fwph_direction",
+           "phgpu_fwph_column", "phgpu_fwph_diff"]
 
 _lib = None
 
@@ -133,6 +143,12 @@ def load(path=None):
     lib.phgpu_rho_ratio_stats.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     lib.phgpu_rho_from_stats.argtypes = [c_vp, c_vp, c_i64, c_dbl, c_vp, c_dbl, c_vp, c_vp, c_vp]
     lib.phgpu_fixer_step.argtypes = [c_vp, ctypes.POINTER(FixerParams)] + [c_vp] * 10
+    lib.phgpu_fwph_init.argtypes = [c_vp, c_i32, c_vp]
+    lib.phgpu_fwph_load.argtypes = [c_vp, c_i32] + [c_vp] * 7
+    lib.phgpu_fwph_export.argtypes = [c_vp] + [c_vp] * 9
+    lib.phgpu_fwph_direction.argtypes = [c_vp, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp]
+    lib.phgpu_fwph_column.argtypes = [c_vp, ctypes.POINTER(FwphParams), c_int] + [c_vp] * 15
+    lib.phgpu_fwph_diff.argtypes = [c_vp, c_vp, c_vp, c_vp]
     lib.phgpu_ipm_info.argtypes = [c_vp, ctypes.POINTER(c_dbl)]
     lib.phgpu_ipm_prof.argtypes = [c_vp, ctypes.POINTER(ctypes.c_ulonglong), c_i64]
     lib.phgpu_ipm_prof.restype = c_i64

@@ -17,6 +17,8 @@ GPU, scenario-fastest ``[k, S]``) and sequences the per-PH-iteration work:
                                                        (utils/gradient.py, find_rho.py, wtracker.py,
                                                         extensions/gradient_extension.py)
     fixer           -> phgpu_fixer_step               (extensions/fixer.py:114-304)
+    FWPH            -> phgpu_fwph_direction, phgpu_fwph_column, phgpu_fwph_diff over the handle's
+                       column store                   (fwph/fwph.py:210-370, 528-547)
 
 All launches go to torch's current stream; host synchronisation happens only where
 the reference needs a host scalar (the convergence test, bounds).
@@ -1118,6 +1120,129 @@ class PHEngine:
             return 0, 0, 0
         t = self.fixer_totals.cpu().tolist()
         return int(t[0]), int(t[1]), int(t[2])
+
+    # -------------------------------------------------------------- FWPH
+    def fwph_init(self, max_cols):
+        """The FWPH column store and its buffers (phgpu_fwph_init; fwph.py:685-771): ``fw_What``
+        (the LP's dual weights, device [nn, S]), ``fw_xq`` ([nn, S]) and ``fw_xqx`` ([n, S],
+        the QP point in x's nonant columns, what the x̄ / W step reads), ``fw_gamma``,
+        ``fw_dual_bound``, ``fw_ncols`` ([S]) and the pinned ``fw_counts`` (int32[4]: still
+        active, Gamma < -stop_check_tol, LP not OPTIMAL)."""
+        self._flush_step()
+        _lib.check(self.lib.phgpu_fwph_init(self.h, int(max_cols), self._stream()), "phgpu_fwph_init")
+        if getattr(self, "fw_What", None) is None:
+            z = lambda *s: torch.zeros(*s, dtype=torch.float64, device=self.device)  # noqa: E731
+            self.fw_What = torch.zeros_like(self.W)
+            self.fw_xq = torch.zeros_like(self.W)
+            self.fw_xqx = torch.zeros_like(self.x)
+            self.fw_gamma = z(self.S)
+            self.fw_dual_bound = z(self.S)
+            self.fw_diff = z(1)
+            self.fw_exp = z(5)
+            self.fw_ncols = torch.zeros(self.S, dtype=torch.int32, device=self.device)
+            self.fw_counts = torch.zeros(4, dtype=torch.int32).pin_memory()
+            self._fw_counts_np = self.fw_counts.numpy()
+            self._fw_ev = torch.cuda.Event()
+        self.fw_max_cols = int(max_cols)
+        self.calls.setdefault("fwph_column", 0)
+        self.calls.setdefault("fwph_direction", 0)
+
+    def fwph_load(self, X, f, a=None):
+        """Fill every scenario's store with K columns (phgpu_fwph_load): X device [K, nn, S],
+        f device [K, S], a device [K, S] or None (all weight on column 0); rho is the engine's."""
+        K = int(X.shape[0])
+        X = X.to(device=self.device, dtype=torch.float64).contiguous()
+        f = f.to(device=self.device, dtype=torch.float64).contiguous()
+        assert tuple(X.shape) == (K, max(self.nn, 1), self.S) and tuple(f.shape) == (K, self.S), (X.shape, f.shape)
+        if a is not None:
+            a = a.to(device=self.device, dtype=torch.float64).contiguous()
+            assert tuple(a.shape) == (K, self.S), a.shape
+        _lib.check(self.lib.phgpu_fwph_load(self.h, K, _ptr(X), _ptr(f), _ptr(a), _ptr(self.rho), _ptr(self.fw_xq),
+                                            _ptr(self.fw_xqx), self._stream()), "phgpu_fwph_load")
+
+    def fwph_export(self):
+        """The store on the host (tests, reporting): dict of X [K, nn, S], f, a [K, S], ncols,
+        phi, active, nit [S] and xq [nn, S] numpy arrays.  Synchronises."""
+        K, S, nn = self.fw_max_cols, self.S, max(self.nn, 1)
+        d = {"X": torch.zeros(K, nn, S, dtype=torch.float64, device=self.device),
+             "f": torch.zeros(K, S, dtype=torch.float64, device=self.device),
+             "a": torch.zeros(K, S, dtype=torch.float64, device=self.device),
+             "ncols": torch.zeros(S, dtype=torch.int32, device=self.device),
+             "xq": torch.zeros(nn, S, dtype=torch.float64, device=self.device),
+             "phi": torch.zeros(S, dtype=torch.float64, device=self.device),
+             "active": torch.zeros(S, dtype=torch.int32, device=self.device),
+             "nit": torch.zeros(S, dtype=torch.int32, device=self.device)}
+        _lib.check(self.lib.phgpu_fwph_export(self.h, *(_ptr(d[k]) for k in ("X", "f", "a", "ncols", "xq", "phi",
+                                                                             "active", "nit")), self._stream()),
+                   "phgpu_fwph_export")
+        return {k: v.cpu().numpy() for k, v in d.items()}
+
+    def fwph_direction(self, t0, alpha):
+        """fw_What = W + rho (src - x̄) (phgpu_fwph_direction, fwph.py:227-247).  Device work only."""
+        self.calls["fwph_direction"] += 1
+        _lib.check(self.lib.phgpu_fwph_direction(self.h, 1 if t0 else 0, float(alpha), _ptr(self.W), _ptr(self.rho),
+                                                 _ptr(self.xbar), _ptr(self.fw_What), self._stream()),
+                   "phgpu_fwph_direction")
+
+    def fwph_bind(self, on):
+        """Bind fw_What (``on``) or W as the solves' dual weights, W on and prox off."""
+        self.W_on, self.prox_on = 1, 0
+        _lib.check(self.lib.phgpu_set_ph_state(self.h, _ptr(self.fw_What if on else self.W), _ptr(self.rho),
+                                               _ptr(self.xbar), 1, 0), "phgpu_set_ph_state")
+
+    def fwph_column(self, params, t0):
+        """One column pass over the last solve (phgpu_fwph_column, fwph.py:256-292); the three
+        counts go to the pinned ``fw_counts`` (``fwph_counts`` waits for them).  ``params``:
+        _lib.FwphParams.  Device work only."""
+        self.calls["fwph_column"] += 1
+        self._fw_counts_np[:] = -1
+        _lib.check(self.lib.phgpu_fwph_column(self.h, ctypes.byref(params), 1 if t0 else 0, _ptr(self.x),
+                                              _ptr(self.obj), _ptr(self.bound), _ptr(self.status), _ptr(self.W),
+                                              _ptr(self.fw_What), _ptr(self.rho), _ptr(self.xbar), _ptr(self.fw_gamma),
+                                              _ptr(self.fw_dual_bound), _ptr(self.fw_ncols), _ptr(self.fw_xq),
+                                              _ptr(self.fw_xqx), _ptr(self.fw_counts), self._stream()),
+                   "phgpu_fwph_column")
+        self._fw_ev.record()
+
+    def fwph_counts(self):
+        """(still active, Gamma < -stop_check_tol, LP not OPTIMAL) of the last column pass over
+        the local scenarios: a wait for the pass and a read of pinned memory, no copy."""
+        self._fw_ev.synchronize()
+        c = self._fw_counts_np
+        return int(c[0]), int(c[1]), int(c[2])
+
+    def fwph_diff(self):
+        """sum_s prob_s sum_k (xq - x̄)^2 with the current (old) x̄, summed over the ranks
+        (phgpu_fwph_diff, fwph.py:528-547): a device [1] tensor."""
+        _lib.check(self.lib.phgpu_fwph_diff(self.h, _ptr(self.xbar), _ptr(self.fw_diff), self._stream()),
+                   "phgpu_fwph_diff")
+        if self.comm.size > 1:
+            self._ar(self.fw_diff)
+        return self.fw_diff
+
+    def fwph_bound(self):
+        """sum_s prob_s dual_bound_s over all ranks (fwph.py:519-526), a host float."""
+        _lib.check(self.lib.phgpu_expectations(self.h, _ptr(self.fw_dual_bound), _ptr(self.fw_dual_bound),
+                                               _ptr(self.status), _ptr(self.fw_exp), self._stream()),
+                   "phgpu_expectations")
+        self.comm.allreduce_sum_(self.fw_exp)
+        return float(self.fw_exp[1].item())
+
+    def fwph_xbar_step(self, update_W):
+        """x̄ from the QP points and, with ``update_W``, W += rho (xq - x̄): phgpu_ph_reduce and
+        phgpu_ph_update_ex on ``fw_xqx`` in place of x (fwph.py:120-121, 187, 198)."""
+        self._flush_xbar()
+        self._ahead_id = 0
+        self.calls["ph_reduce"] += 1
+        _lib.check(self.lib.phgpu_ph_reduce(self.h, _ptr(self.fw_xqx), _ptr(self.node_buf), self._stream()),
+                   "phgpu_ph_reduce")
+        if self.comm.size > 1:
+            self.calls["allreduce_xbar"] += 1
+        self._allreduce_sum_(self.node_buf)
+        self.calls["ph_update_ex"] += 1
+        _lib.check(self.lib.phgpu_ph_update_ex(self.h, _ptr(self.fw_xqx), _ptr(self.node_buf), _ptr(self.xbar),
+                                               _ptr(self.W), _ptr(self.rho), 1 if update_W else 0,
+                                               _ptr(self.conv_buf), None, self._stream()), "phgpu_ph_update_ex")
 
     def fix_nonants_by_node(self, table):
         """Fix every local scenario's nonants at per-node values: ``table`` is a device

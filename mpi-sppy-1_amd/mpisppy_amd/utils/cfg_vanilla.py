@@ -1,5 +1,5 @@
 """Cylinder dict builders (mirrors mpisppy/utils/cfg_vanilla.py:41-495 for the cylinders
-this engine serves: ph_hub, lagrangian_spoke, xhatshuffle_spoke, xhatxbar_spoke,
+this engine serves: ph_hub, fwph_spoke, lagrangian_spoke, xhatshuffle_spoke, xhatxbar_spoke,
 slammax_spoke, slammin_spoke; extension_adder, add_fixer and add_wxbar_read_write for the hub's
 extensions).
 
@@ -9,6 +9,7 @@ defaults.  The returned dicts feed ``WheelSpinner(hub_dict, list_of_spoke_dict)`
 """
 import copy
 
+from ..cylinders.fwph_spoke import FrankWolfeOuterBound
 from ..cylinders.hub import PHHub
 from ..cylinders.lagrangian_bounder import LagrangianOuterBound
 from ..cylinders.slam_heuristic import SlamMaxHeuristic, SlamMinHeuristic
@@ -21,6 +22,7 @@ from ..extensions.fixer import Fixer
 from ..extensions.gradient_extension import Gradient_extension
 from ..extensions.mult_rho_updater import MultRhoUpdater
 from ..extensions.norm_rho_updater import NormRhoUpdater
+from ..fwph.fwph import FWPH
 from ..opt.ph import PH
 from ..phbase import PHBase
 from .xhat_eval import Xhat_Eval
@@ -79,6 +81,43 @@ def ph_hub(cfg, scenario_creator, scenario_denouement, all_scenario_names, scena
             "extensions": ph_extensions,
             "extension_kwargs": extension_kwargs,
             "ph_converger": ph_converger,
+            "all_nodenames": all_nodenames,
+        },
+    }
+
+
+# cfg_vanilla.py:277-317
+def fwph_spoke(cfg, scenario_creator, scenario_denouement, all_scenario_names, scenario_creator_kwargs=None,
+               all_nodenames=None):
+    shoptions = shared_options(cfg)
+    mip_solver_options, qp_solver_options = dict(), dict()
+    if getattr(cfg, "max_solver_threads", None) is not None:
+        mip_solver_options["threads"] = cfg.max_solver_threads
+        qp_solver_options["threads"] = cfg.max_solver_threads
+    if getattr(cfg, "fwph_mipgap", None) is not None:
+        mip_solver_options["mipgap"] = cfg.fwph_mipgap      # accepted and ignored: the "MIP" is an LP here
+    fw_options = {
+        "FW_iter_limit": _get(cfg, "fwph_iter_limit", 10),
+        "FW_weight": _get(cfg, "fwph_weight", 0.0),
+        "FW_conv_thresh": _get(cfg, "fwph_conv_thresh", 1e-4),
+        "stop_check_tol": _get(cfg, "fwph_stop_check_tol", 1e-4),
+        "solver_name": shoptions["solver_name"],
+        "FW_verbose": shoptions["verbose"],
+        "mip_solver_options": mip_solver_options,
+        "qp_solver_options": qp_solver_options,
+    }
+    if getattr(cfg, "fwph_max_columns", None) is not None:
+        fw_options["FW_max_columns"] = cfg.fwph_max_columns
+    return {
+        "spoke_class": FrankWolfeOuterBound,
+        "opt_class": FWPH,
+        "opt_kwargs": {
+            "PH_options": shoptions,  # be sure convthresh is zero for fwph
+            "FW_options": fw_options,
+            "all_scenario_names": all_scenario_names,
+            "scenario_creator": scenario_creator,
+            "scenario_creator_kwargs": scenario_creator_kwargs,
+            "scenario_denouement": scenario_denouement,
             "all_nodenames": all_nodenames,
         },
     }

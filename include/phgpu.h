@@ -18,6 +18,11 @@
  *                                          mpisppy/extensions/fixer.py:114-304 -> phgpu_fixer_step
  *   - FWPH's column set and QP per scenario (SDM, _add_QP_column, _conv_diff)
  *                                          mpisppy/fwph/fwph.py:210-370, 528-547 -> phgpu_fwph_*
+ *   - APH's projective step, dispatch and partial solve loop (Update_y, Compute_Averages,
+ *     listener_side_gig, Update_theta_zw, _dispatch_list, APH_solve_loop)
+ *                                          mpisppy/opt/aph.py:151-195, 254-310, 394-408, 453-496,
+ *                                          602-668 -> phgpu_aph_*, phgpu_select_smallest,
+ *                                          phgpu_solve_list
  *
  * The cross-rank sums (the per-node MPI Allreduce of phbase.py:83-87 and the
  * ROOT-comm Allreduce of phbase.py:341) are done by the caller (RCCL all-reduce of
@@ -587,6 +592,101 @@ int phgpu_fwph_column(phgpu_handle h, const phgpu_fwph_params* prm, int t0, cons
  * per-block sums in a fixed order, the blocks' sums by a fixed tree in the block with the last
  * ticket (as phgpu_w_diff).  out: device double[1]. */
 int phgpu_fwph_diff(phgpu_handle h, const double* xbar, double* out, void* stream);
+
+/* APH (mpisppy/opt/aph.py): everything of one iteration around the subproblem solves, for all
+ * local scenarios.  The reference walks its scenarios and nonants in Python four times per
+ * iteration (Update_y, Compute_Averages, listener_side_gig, Update_theta_zw), sorts a Python list
+ * for the dispatch (:602-632) and calls a solver per dispatched scenario (:642-657); here each is
+ * one device pass.  y, z, u and the lagged copies are caller-owned device arrays [nn*S], k-major
+ * and scenario-fastest like W; phi, k1, last_phi are [S] doubles; mask, list, last_iter [S] int32.
+ * All entries are ordered on the stream and never synchronise, work for any tree and any nn and
+ * on a PHGPU_SHARED_MATRIX handle (phgpu_solve_list excepted, see there), use the per-nonant
+ * probabilities of phgpu_set_nonant_probs in the node sums where they are set (as
+ * phgpu_nonant_stats), and give the same bits on every run.  Each allocates its own workspace at
+ * its first call (phgpu_workspace_bytes grows only then).  A step deferred by phgpu_ph_step_defer
+ * is run first.  The ranks' sums are the caller's.
+ *
+ * phgpu_aph_reduce: Update_y (aph.py:151-181) and the local sums of Compute_Averages (:394-408)
+ * in one pass.  With first (the reference's _PHIter == 1) y = 0 everywhere; else
+ *   y[k, s] = W_use[k, s] + rho[k, s] (x[col_k, s] - z_use[k, s])   where mask[s] != 0
+ * (mask NULL: every scenario), and y is kept elsewhere.  W_use / z_use: W and z, or the lagged
+ * copies under APHuse_lag (unused with first, may be NULL then).
+ *   planes[3 * num_nodes * nlen_max]: three planes, each laid out like one half of node_buf,
+ *   over the local scenarios:  sum pcoef x,  sum pcoef x^2,  sum pcoef y  (pcoef: prob_coeff of the
+ *   nonant's node, or pvar).  An entry without a nonant is 0.  The node-segmented sum of
+ *   phgpu_ph_reduce with three planes: per-wave partials and an ordered final sum where a wave's
+ *   scenarios share a node (deterministic); waves that span nodes add by fp64 atomics, exactly
+ *   as phgpu_ph_reduce documents. */
+int phgpu_aph_reduce(phgpu_handle h, int first, const int32_t* mask, const double* x, const double* W_use,
+                     const double* z_use, const double* rho, double* y, double* planes, void* stream);
+
+/* The body of listener_side_gig (aph.py:254-310) after the ranks' sum of the three planes:
+ *   xbar[k, s] = plane 0 at the scenario's node entry (scattered),  u[k, s] = x[col_k, s] - xbar[k, s],
+ *   phi[s] = p_s sum_k (z - x)(W - y)          (compute_phis_summand, :185-195),
+ *   out[4] = { sum_s p_s (|u_s|^2 + |ybar_s|^2 / gamma),  sum_s phi_s,  sum_s p_s |u_s|^2,
+ *              sum_s p_s |ybar_s|^2 }          (tau's, phi's, pusqnorm's and pvsqnorm's summands)
+ * with ybar_s plane 2 at the scenario's node entries and p_s the scenario's probability.  The sums
+ * are per thread in index order, per block in a fixed order and over the blocks by the one with
+ * the last ticket (as phgpu_w_diff).  out: device double[4] (or host-mapped), stored by one
+ * instruction.  gamma > 0. */
+int phgpu_aph_norms(phgpu_handle h, double gamma, const double* planes, const double* x, const double* y,
+                    const double* W, const double* z, double* xbar, double* u, double* phi, double* out,
+                    void* stream);
+
+/* Update_theta_zw (aph.py:453-496) after the ranks' sum of phgpu_aph_norms' scalars.  red: device
+ * double[>= 2] = {tau, phi} reduced; theta is computed on the device, no read-back:
+ *   theta = phi nu / tau if tau > 0 and phi > 0, else 0;
+ *   W += theta u;   z = xbar (plane 0) with first, else z += theta ybar / gamma;
+ *   phi[s] = p_s sum_k (z - x)(W - y) with the new W and z: what the dispatch sorts by (:756);
+ *   out[4] = { sum_s p_s |W_s|^2,  sum_s p_s |z_s|^2,  theta,  sum_s phi_s }.
+ * out may be host-mapped pinned memory; it is written last, by one store instruction (the
+ * contract of conv_local in phgpu_ph_update_ex).  Sums as in phgpu_aph_norms. */
+int phgpu_aph_update(phgpu_handle h, int first, double nu, double gamma, const double* red,
+                     const double* planes, const double* x, const double* y, const double* u, double* W,
+                     double* z, double* phi, double* out, void* stream);
+
+/* The dispatch bookkeeping of APH_solve_loop for the scenarios with mask[s] != 0 (aph.py:646:
+ * dispatchrecord gets (iter, phi); _update_foropt :529-550), called after their solve:
+ *   last_iter[s] = iter,  last_phi[s] = phi[s],  W_lag[., s] = W[., s],  z_lag[., s] = z[., s]
+ * (W_lag and z_lag both NULL: no copies), and for EVERY scenario the first sort key of the next
+ * dispatch, as the reference writes its two orders:
+ *   round_robin == 0 (:626-629):  k1[s] = -max(last_iter[s], shelf_life - 1)   (second key: phi)
+ *   round_robin != 0 (:610-611):  k1[s] = last_iter[s]                         (second key: last_phi)
+ * The first of these prefers the scenarios dispatched most recently once iterations pass
+ * shelf_life - 1; it is kept as written. */
+int phgpu_aph_mark(phgpu_handle h, const int32_t* mask, int32_t iter, int32_t shelf_life, int round_robin,
+                   const double* phi, int32_t* last_iter, double* last_phi, double* k1, const double* W,
+                   const double* z, double* W_lag, double* z_lag, void* stream);
+
+/* Mark the count local scenarios that are smallest by the lexicographic key (k1[s], k2[s], s):
+ * what Python's stable sorted() over the reference's dict order takes first (aph.py:610-629).
+ *   k1: device double[S] or NULL (all equal); k2: device double[S]; 1 <= count <= S < 2^31;
+ *   mask: device int32[S], 1 for the taken scenarios and 0 for the others;
+ *   list: device int32[count], the taken scenarios in ascending s.
+ * Keys are finite doubles (-0.0 equals 0.0); what a NaN gives is unspecified (nothing is
+ * written out of bounds).  No host read-back: a radix select on the order-preserving 64-bit image
+ * of the keys, most significant digit first (6 histogram passes per key over a grid of at most 64
+ * workgroups, k1 first, k2 among k1's ties), then a ballot / prefix compaction over the grid
+ * that takes the first remaining exact ties in index order.  Histograms and counters are
+ * integers: the same result on every run. */
+int phgpu_select_smallest(phgpu_handle h, const double* k1, const double* k2, int32_t count, int32_t* mask,
+                          int32_t* list, void* stream);
+
+/* A warm solve of the listed scenarios only, in place (the partial APH_solve_loop, aph.py:642-657):
+ * their entries of x, y, obj, bound, status, iters (the buffers of the previous phgpu_solve) and
+ * their warm-start state are replaced; no other scenario's entry of the caller's buffers or of
+ * the handle's warm state is touched.
+ *   list: device int32[count], ascending and distinct; 0 <= count <= S.
+ * It runs on a PDHG kernel with a list mode: path 5 of the handle's path-6 module where path 6 is
+ * the default (the kernel that serves path 6's fallback list), the handle's path-5 module where
+ * that is the default, else the global-memory kernel (path 1).  A warm state held in the records
+ * (paths 2r, 3) is taken out first; the path-6 epilogue's x̄ partials are invalidated; an
+ * uncommitted phgpu_solve_deferred is dropped; the solve is not deferrable.  A full dispatch
+ * (count == S) is better served by phgpu_solve, which stays on the handle's default path.
+ * Returns 0 and launches nothing for count == 0; -3 on a PHGPU_SHARED_MATRIX handle (the
+ * streaming kernel has no list mode yet); -1 before any solve (there is no warm state). */
+int phgpu_solve_list(phgpu_handle h, const phgpu_options* opt, const int32_t* list, int32_t count, double* x,
+                     double* y, double* obj, double* bound, int32_t* status, int32_t* iters, void* stream);
 
 /* Free the workspace and the handle. */
 int phgpu_destroy(phgpu_handle h);

@@ -21,6 +21,8 @@
 //                                       utils/gradient.py:65-81, utils/wtracker.py:134-157,
 //                                       utils/find_rho.py:78-203,
 //                                       extensions/gradient_extension.py:65-95
+//   APH's projective step, dispatch and partial solve loop
+//                                       opt/aph.py:151-195, 254-310, 394-408, 453-496, 602-668
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -69,6 +71,7 @@ static int set_err(int code, const char* fmt, ...) {
 struct jit_module;  // solve_jit.inc: the hipRTC-compiled path-5 kernel of a handle
 struct ipm_module;  // solve_ipm.inc: the hipRTC-compiled path-6 module of a handle
 struct fwph_store;  // ph_fwph.inc: the FWPH column store of a handle
+struct sel_state;   // ph_aph.inc: the workspace of phgpu_select_smallest
 struct ph_ws {      // a reduction's device workspace: partials, and node tags or a ticket counter
     double* part;
     int32_t* tag;
@@ -251,6 +254,12 @@ struct phgpu_state {
     // phgpu_fwph_init) and the per-block partials and ticket of phgpu_fwph_diff
     fwph_store* fw;
     ph_ws fwd;
+    // phgpu_aph_*: the per-wave partials of phgpu_aph_reduce (3 planes), the per-block partials
+    // and tickets of phgpu_aph_norms and phgpu_aph_update; phgpu_select_smallest's workspace;
+    // the list length of phgpu_solve_list on the device.  Each allocated at its entry's first call.
+    ph_ws apr, apn, apu;
+    sel_state* sel;
+    int32_t* list_n;
 };
 
 // ------------------------------------------------------------------ ownership (host)
@@ -1107,6 +1116,7 @@ __global__ void k_stats_copy(const unsigned long long* __restrict__ src, int cop
 #include "ph_reduce.inc"
 #include "ph_fixer.inc"
 #include "ph_fwph.inc"
+#include "ph_aph.inc"
 
 // Xhat_Eval._fix_nonants (utils/xhat_eval.py; spopt.py _fix_nonants): nonant columns of
 // every scenario get lb = ub = xfix[k, s] (scaled); xfix == NULL restores the model bounds.
@@ -2124,6 +2134,19 @@ static int default_path(const phgpu_state* h) {
 
 #include "solve_launch.inc"
 
+// the options of a solve (null: the defaults), checked
+static int solve_options(const phgpu_options* opt, phgpu_options& o) {
+    if (opt) o = *opt;
+    else phgpu_default_options(&o);
+    if (o.check_every < 1 || o.max_iter < 1 || !(o.eta_frac > 0.0 && o.eta_frac < 1.0) ||
+        o.gamma < 0.0 || o.gamma > 1.0 || o.restart_every < 1 || o.check_every % o.restart_every != 0 ||
+        o.max_iter % o.restart_every != 0 || !(o.eps_infeas > 0.0))
+        return set_err(-1, "bad options (check_every=%d restart_every=%d max_iter=%d eta_frac=%g gamma=%g "
+                       "eps_infeas=%g; check_every and max_iter must be multiples of restart_every)",
+                       o.check_every, o.restart_every, o.max_iter, o.eta_frac, o.gamma, o.eps_infeas);
+    return 0;
+}
+
 static int solve_impl(phgpu_handle h, const phgpu_options* opt, int warm_start, int defer, double* x, double* y,
                       double* obj, double* bound, int32_t* status, int32_t* iters, void* stream) {
     if (!h) return set_err(-1, "null handle");
@@ -2136,14 +2159,10 @@ static int solve_impl(phgpu_handle h, const phgpu_options* opt, int warm_start, 
     h->wq = defer ? 1 - h->wslot : h->wslot;
     bind_slots(h);
     phgpu_options o;
-    if (opt) o = *opt;
-    else phgpu_default_options(&o);
-    if (o.check_every < 1 || o.max_iter < 1 || !(o.eta_frac > 0.0 && o.eta_frac < 1.0) ||
-        o.gamma < 0.0 || o.gamma > 1.0 || o.restart_every < 1 || o.check_every % o.restart_every != 0 ||
-        o.max_iter % o.restart_every != 0 || !(o.eps_infeas > 0.0))
-        return set_err(-1, "bad options (check_every=%d restart_every=%d max_iter=%d eta_frac=%g gamma=%g "
-                       "eps_infeas=%g; check_every and max_iter must be multiples of restart_every)",
-                       o.check_every, o.restart_every, o.max_iter, o.eta_frac, o.gamma, o.eps_infeas);
+    {
+        const int orc = solve_options(opt, o);
+        if (orc) return orc;
+    }
     const solve_params P = make_solve_params(o, (warm_start && h->have_solution) ? 1 : 0);
     hipStream_t st = (hipStream_t)stream;
     // the register-resident kernels are specialised for the reflected step (gamma = 1, the
@@ -3036,6 +3055,183 @@ extern "C" int phgpu_fwph_diff(phgpu_handle h, const double* xbar, double* out, 
     hipLaunchKernelGGL(k_fw_diff, dim3((unsigned)nblk), dim3(GR_T), 0, st, *h, *h->fw, xbar, h->fwd.part, h->fwd.tag,
                        out);
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------ APH (ph_aph.inc)
+// aph.py:151-181 and 394-408
+extern "C" int phgpu_aph_reduce(phgpu_handle h, int first, const int32_t* mask, const double* x, const double* W_use,
+                                const double* z_use, const double* rho, double* y, double* planes, void* stream) {
+    if (!h || !x || !y || !planes || (!first && (!W_use || !z_use || !rho))) return set_err(-1, "null argument");
+    FLUSH_STEP(h);
+    hipStream_t st = (hipStream_t)stream;
+    return node_reduce<0, AP_NV>(h, h->apr, planes, nullptr, st, [&] {
+        dim3 g = grid_for(h->S);
+        g.y = (unsigned)h->nn;
+        hipLaunchKernelGGL(k_aph_reduce_partial, g, dim3(BLOCK), 0, st, *h, h->apr, first ? 1 : 0, mask, x, W_use,
+                           z_use, rho, y, planes);
+    });
+}
+
+static inline unsigned aph_blocks(const phgpu_state* h) {
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((h->S + GR_T - 1) / GR_T, WD_BLOCKS));
+}
+
+// aph.py:254-310 and 185-195
+extern "C" int phgpu_aph_norms(phgpu_handle h, double gamma, const double* planes, const double* x, const double* y,
+                               const double* W, const double* z, double* xbar, double* u, double* phi, double* out,
+                               void* stream) {
+    if (!h || !planes || !x || !y || !W || !z || !xbar || !u || !phi || !out) return set_err(-1, "null argument");
+    if (!(gamma > 0.0)) return set_err(-1, "phgpu_aph_norms: gamma %g is not positive", gamma);
+    FLUSH_STEP(h);
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = ticket_ws(h, h->apn, (size_t)4 * WD_BLOCKS, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_aph_norms, dim3(aph_blocks(h)), dim3(GR_T), 0, st, *h, gamma, planes, x, y, W, z, xbar, u, phi,
+                       h->apn.part, h->apn.tag, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// aph.py:453-496 and 756
+extern "C" int phgpu_aph_update(phgpu_handle h, int first, double nu, double gamma, const double* red,
+                                const double* planes, const double* x, const double* y, const double* u, double* W,
+                                double* z, double* phi, double* out, void* stream) {
+    if (!h || !red || !planes || !x || !y || !u || !W || !z || !phi || !out) return set_err(-1, "null argument");
+    if (!(gamma > 0.0)) return set_err(-1, "phgpu_aph_update: gamma %g is not positive", gamma);
+    FLUSH_STEP(h);
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = ticket_ws(h, h->apu, (size_t)3 * WD_BLOCKS, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_aph_update, dim3(aph_blocks(h)), dim3(GR_T), 0, st, *h, first ? 1 : 0, nu, gamma, red, planes,
+                       x, y, u, W, z, phi, h->apu.part, h->apu.tag, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// aph.py:646, 529-550 and the sort keys of :610-611 and :626-629
+extern "C" int phgpu_aph_mark(phgpu_handle h, const int32_t* mask, int32_t iter, int32_t shelf_life, int round_robin,
+                              const double* phi, int32_t* last_iter, double* last_phi, double* k1, const double* W,
+                              const double* z, double* W_lag, double* z_lag, void* stream) {
+    if (!h || !mask || !phi || !last_iter || !last_phi || !k1) return set_err(-1, "null argument");
+    if ((W_lag != nullptr) != (z_lag != nullptr) || (W_lag && (!W || !z)))
+        return set_err(-1, "phgpu_aph_mark: the lagged copies need W, z, W_lag and z_lag");
+    FLUSH_STEP(h);
+    hipLaunchKernelGGL(k_aph_mark, dim3(aph_blocks(h)), dim3(GR_T), 0, (hipStream_t)stream, *h, mask, (int)iter,
+                       (int)shelf_life, round_robin ? 1 : 0, phi, last_iter, last_phi, k1, W, z, W_lag, z_lag);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// the dispatch list of aph.py:602-632
+extern "C" int phgpu_select_smallest(phgpu_handle h, const double* k1, const double* k2, int32_t count, int32_t* mask,
+                                     int32_t* list, void* stream) {
+    if (!h || !k2 || !mask || !list) return set_err(-1, "null argument");
+    if (h->S >= (1LL << 31) || count < 1 || (int64_t)count > h->S)
+        return set_err(-1, "phgpu_select_smallest: count %d of %lld scenarios", (int)count, (long long)h->S);
+    FLUSH_STEP(h);
+    hipStream_t st = (hipStream_t)stream;
+    if (!h->sel) {
+        const int rc = dalloc(h, &h->sel, 1);
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync(h->sel, 0, sizeof(sel_state), st));
+    }
+    const int64_t S = h->S;
+    // four scenarios per thread before the grid is capped
+    const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>((S + 4 * SEL_T - 1) / (4 * SEL_T), SEL_BLOCKS));
+    int cnt0 = count;  // (the first launch starts the state)
+    for (int which = k1 ? 0 : 1; which < 2; ++which)
+        for (int pass = 0; pass < SEL_PASSES; ++pass) {
+            hipLaunchKernelGGL(k_sel_pass, dim3(nb), dim3(SEL_T), 0, st, S, k1, k2, which, pass, cnt0, h->sel);
+            cnt0 = 0;
+        }
+    const int64_t ne = std::max<int64_t>(1, std::min<int64_t>((S + SEL_T - 1) / SEL_T, SEL_EMIT_BLOCKS));
+    const int64_t chunk = (((S + ne - 1) / ne + SEL_T - 1) / SEL_T) * SEL_T;
+    hipLaunchKernelGGL(k_sel_count, dim3((unsigned)ne), dim3(SEL_T), 0, st, S, chunk, k1, k2, h->sel);
+    hipLaunchKernelGGL(k_sel_emit, dim3((unsigned)ne), dim3(SEL_T), 0, st, S, chunk, (int)count, k1, k2,
+                       (const sel_state*)h->sel, mask, list);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// A warm solve of the listed scenarios only, in place, on a kernel with a list mode: path 5 of
+// the handle's path-6 module where path 6 is the default (as ipm_fallback_launch binds it), the
+// handle's own path-5 module where that is the default, else k_solve
+extern "C" int phgpu_solve_list(phgpu_handle h, const phgpu_options* opt, const int32_t* list, int32_t count,
+                                double* x, double* y, double* obj, double* bound, int32_t* status, int32_t* iters,
+                                void* stream) {
+    if (!h) return set_err(-1, "null handle");
+    if (count < 0 || (int64_t)count > h->S)
+        return set_err(-1, "phgpu_solve_list: %d entries for %lld scenarios", (int)count, (long long)h->S);
+    if (count == 0) return 0;
+    if (h->shared)
+        return set_err(-3, "phgpu_solve_list: a shared-matrix handle (path 4) has no list mode");
+    if (!list || !x || !obj || !bound || !status) return set_err(-1, "null argument");
+    FLUSH_STEP(h);
+    // in place in the committed slot; an uncommitted deferred solve is dropped
+    h->pending = -1;
+    h->wq = h->wslot;
+    bind_slots(h);
+    if (!h->have_solution) return set_err(-1, "phgpu_solve_list: a warm solve, and no solve has run yet");
+    phgpu_options o;
+    {
+        const int orc = solve_options(opt, o);
+        if (orc) return orc;
+    }
+    const solve_params P = make_solve_params(o, 1);
+    hipStream_t st = (hipStream_t)stream;
+    if (!h->list_n) {
+        const int rc = dalloc(h, &h->list_n, 1);
+        if (rc) return rc;
+    }
+    int rc = warm_from_records(h, P, st);
+    if (rc) return rc;
+    hipFunction_t fn = nullptr;
+    int per_cu = 0;
+    if (o.gamma == 1.0) {
+        const int path = default_path(h);
+        if (path == 6 && ipm_prepare(h, st) == 0 && h->ipm->fn_pdhg) {
+            fn = h->ipm->fn_pdhg;
+            per_cu = h->ipm->per_cu_pdhg;
+        } else if (path == 5) {
+            rc = jit_prepare(h, st);
+            if (rc) return rc;
+            fn = h->jit->fn;
+            per_cu = h->jit->per_cu;
+        }
+    }
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)h->list_n, (int)count, 1, st));
+    if (fn) {
+        jit_params a{};
+        a.A = h->Ah_csr; a.c = h->c; a.q = h->q; a.Dc = h->Dc; a.lbh = h->lbh; a.ubh = h->ubh; a.Dr = h->Dr;
+        a.rlh = h->rlh; a.ruh = h->ruh; a.rl = h->rl; a.ru = h->ru; a.objc = h->objc; a.normA = h->normA;
+        a.W = h->W; a.rho = h->rho; a.xbar = h->xbar;
+        a.omega_in = h->omega; a.x_in = h->x; a.y_in = h->y;
+        a.omega_out = h->omega_w; a.x_w = h->xw; a.y_w = h->yw;
+        a.xout = x; a.yout = y; a.obj = obj; a.bound = bound;
+        a.status = status; a.iters = iters; a.qhead = h->qhead;
+        a.list = list; a.list_n = h->list_n; a.stats = nullptr;
+        a.S = h->S;
+        a.W_on = h->W_on; a.prox_on = h->prox_on;
+        a.eps_rel = P.eps_rel; a.eps_abs = P.eps_abs; a.bsuff = P.bsuff; a.bnec = P.bnec; a.bart = P.bart;
+        a.eta_frac = P.eta_frac; a.omega0 = P.omega0; a.wmin = P.wmin; a.wmax = P.wmax; a.eps_inf = P.eps_inf;
+        a.max_iter = P.max_iter; a.check_every = P.check_every; a.restart_every = P.restart_every; a.warm = 1;
+        a.keep_omega = P.keep_omega; a.infeas_start = P.infeas_start;
+        // a persistent grid that drains the list through the queue (first_dyn 0: the kernel's
+        // static first assignment is by scenario index, not by list entry)
+        const int64_t per = (int64_t)(per_cu < 1 ? 1 : per_cu) * h->num_cus * 256;
+        const int64_t nblk = (std::min<int64_t>(per, count) + 255) / 256;
+        a.first_dyn = 0;
+        HIPCHK(hipMemsetAsync(h->qhead, 0, sizeof(int), st));
+        void* args[] = {&a};
+        HIPCHK(hipModuleLaunchKernel(fn, (unsigned)nblk, 1, 1, 256, 1, 1, 0, st, args, nullptr));
+    } else {
+        hipLaunchKernelGGL(k_solve, dim3((unsigned)((count + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, *h, P, x, y, obj,
+                           bound, status, iters, list, (const int32_t*)h->list_n);
+        HIPCHK(hipGetLastError());
+    }
+    h->last_stats = nullptr;
+    solve_done(h, fn ? 5 : 1, 0, 0, status, iters);
     return 0;
 }
 

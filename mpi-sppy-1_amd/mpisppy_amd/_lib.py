@@ -84,7 +84,9 @@ EXPORTS = ["phgpu_default_options", "phgpu_create", "phgpu_create2", "phgpu_set_
            "phgpu_nonant_stats", "phgpu_nonant_closest", "phgpu_grad_cost", "phgpu_w_diff",
            "phgpu_rho_ratio_stats", "phgpu_rho_from_stats", "phgpu_fixer_step",
            "phgpu_fwph_init", "phgpu_fwph_load", "phgpu_fwph_export", "phgpu_fwph_direction",
-           "phgpu_fwph_column", "phgpu_fwph_diff"]
+           "phgpu_fwph_column", "phgpu_fwph_diff",
+           "phgpu_aph_reduce", "phgpu_aph_norms", "phgpu_aph_update", "phgpu_aph_mark",
+           "phgpu_select_smallest", "phgpu_solve_list"]
 
 _lib = None
 
@@ -149,6 +151,12 @@ def load(path=None):
     lib.phgpu_fwph_direction.argtypes = [c_vp, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp]
     lib.phgpu_fwph_column.argtypes = [c_vp, ctypes.POINTER(FwphParams), c_int] + [c_vp] * 15
     lib.phgpu_fwph_diff.argtypes = [c_vp, c_vp, c_vp, c_vp]
+    lib.phgpu_aph_reduce.argtypes = [c_vp, c_int] + [c_vp] * 8
+    lib.phgpu_aph_norms.argtypes = [c_vp, c_dbl] + [c_vp] * 10
+    lib.phgpu_aph_update.argtypes = [c_vp, c_int, c_dbl, c_dbl] + [c_vp] * 10
+    lib.phgpu_aph_mark.argtypes = [c_vp, c_vp, c_i32, c_i32, c_int] + [c_vp] * 9
+    lib.phgpu_select_smallest.argtypes = [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]
+    lib.phgpu_solve_list.argtypes = [c_vp, ctypes.POINTER(PhgpuOptions), c_vp, c_i32] + [c_vp] * 7
     lib.phgpu_ipm_info.argtypes = [c_vp, ctypes.POINTER(c_dbl)]
     lib.phgpu_ipm_prof.argtypes = [c_vp, ctypes.POINTER(ctypes.c_ulonglong), c_i64]
     lib.phgpu_ipm_prof.restype = c_i64

@@ -370,3 +370,16 @@ class PHHub(Hub):
         self._w_snapshot.copy_(W)
         for idx in self.w_spoke_indices:
             self.hub_to_spoke(self._w_snapshot, idx)
+
+
+class APHHub(PHHub):
+    """The hub of APH (reference hub.py:691-751): PHHub's windows and traffic -- W and the
+    nonants out, the bounds in -- around ``APH_main``."""
+
+    def setup_hub(self):
+        super().setup_hub()
+        if not self.has_outerbound_spokes:
+            logger.warning("No OuterBound Spokes defined, this converger will not cause the hub to terminate")
+
+    def main(self):
+        self.opt.APH_main(spcomm=self, finalize=False)

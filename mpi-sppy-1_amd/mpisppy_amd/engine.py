@@ -19,6 +19,9 @@ GPU, scenario-fastest ``[k, S]``) and sequences the per-PH-iteration work:
     fixer           -> phgpu_fixer_step               (extensions/fixer.py:114-304)
     FWPH            -> phgpu_fwph_direction, phgpu_fwph_column, phgpu_fwph_diff over the handle's
                        column store                   (fwph/fwph.py:210-370, 528-547)
+    APH             -> phgpu_aph_reduce + all-reduce, phgpu_aph_norms + all-reduce,
+                       phgpu_aph_update, phgpu_select_smallest, phgpu_solve_list, phgpu_aph_mark
+                                                       (opt/aph.py:151-195, 254-310, 453-496, 602-646)
 
 All launches go to torch's current stream; host synchronisation happens only where
 the reference needs a host scalar (the convergence test, bounds).
@@ -260,7 +263,9 @@ class PHEngine:
         self._bind()
 
     def _bind(self):
-        _lib.check(self.lib.phgpu_set_ph_state(self.h, _ptr(self.W), _ptr(self.rho), _ptr(self.xbar),
+        # (APH binds its own dual weights and prox centre, aph_bind; None: W and x̄)
+        W, centre = getattr(self, "_aph_bound", None) or (self.W, self.xbar)
+        _lib.check(self.lib.phgpu_set_ph_state(self.h, _ptr(W), _ptr(self.rho), _ptr(centre),
                                                self.W_on, self.prox_on), "phgpu_set_ph_state")
 
     def close(self):
@@ -1243,6 +1248,139 @@ class PHEngine:
         _lib.check(self.lib.phgpu_ph_update_ex(self.h, _ptr(self.fw_xqx), _ptr(self.node_buf), _ptr(self.xbar),
                                                _ptr(self.W), _ptr(self.rho), 1 if update_W else 0,
                                                _ptr(self.conv_buf), None, self._stream()), "phgpu_ph_update_ex")
+
+    # -------------------------------------------------------------- APH
+    def aph_init(self, use_lag=False):
+        """The buffers of APH (mpisppy/opt/aph.py) on the device: ``aph_y``, ``aph_z``, ``aph_u``
+        ([nn, S]), ``aph_phi`` ([S]), the three node planes ``aph_planes`` (x̄, E[x²], ȳ, each
+        laid out like half of node_buf), ``aph_red`` ([6]: tau, phi, the four squared norms of
+        the second reduction), the dispatch state ``aph_mask`` / ``aph_list`` (int32 [S]),
+        ``aph_k1``, ``aph_last_iter``, ``aph_last_phi`` ([S]), the pinned ``aph_out`` ([4]: sum
+        p W², sum p z², theta, sum phi of phgpu_aph_update).  With ``use_lag`` (APHuse_lag) also
+        ``aph_W_lag`` / ``aph_z_lag``, every scenario's W and z as of its last dispatch, which
+        are then what Update_y and the solves see."""
+        self._flush_step()
+        z = lambda *s: torch.zeros(*s, dtype=torch.float64, device=self.device)  # noqa: E731
+        zi = lambda *s: torch.zeros(*s, dtype=torch.int32, device=self.device)  # noqa: E731
+        nn, S = max(self.nn, 1), self.S
+        self.aph_use_lag = bool(use_lag)
+        self.aph_y, self.aph_z, self.aph_u = z(nn, S), z(nn, S), z(nn, S)
+        self.aph_phi = z(S)
+        self.aph_planes = z(3 * self.num_nodes * self.nlen_max)
+        self.aph_red = z(6)
+        self.aph_mask, self.aph_list = zi(S), zi(S)
+        self.aph_k1, self.aph_last_phi = z(S), z(S)
+        self.aph_last_iter = zi(S)
+        self.aph_W_lag = z(nn, S) if use_lag else None
+        self.aph_z_lag = z(nn, S) if use_lag else None
+        self.aph_out = torch.zeros(4, dtype=torch.float64).pin_memory()
+        self._aph_out_np = self.aph_out.numpy()
+        self._aph_red_host = torch.zeros(6, dtype=torch.float64).pin_memory()
+        self._aph_ev = torch.cuda.Event()
+        self._aph_bound = None
+        for k in ("aph_reduce", "aph_norms", "aph_update", "aph_mark", "select_smallest", "solve_list",
+                  "allreduce_aph_planes", "allreduce_aph_scalars", "aph_scalars_read"):
+            self.calls.setdefault(k, 0)
+
+    def _aph_use(self):
+        return (self.aph_W_lag, self.aph_z_lag) if self.aph_use_lag else (self.W, self.aph_z)
+
+    def aph_bind(self, on=True):
+        """Bind W and z (their lagged copies under lag) as the solves' dual weights and prox
+        centre, until ``aph_bind(False)``; ``xbar`` stays the engine's x̄ tensor, which spokes
+        and extensions read."""
+        self._aph_bound = self._aph_use() if on else None
+        self._bind()
+
+    def aph_reduce(self, first, mask=None):
+        """Update_y and the first reduction (phgpu_aph_reduce, aph.py:151-181, 394-408): y of the
+        scenarios in ``mask`` (device int32 [S]; None: all) and the ranks' sum of the three
+        planes.  Device work only."""
+        Wu, zu = self._aph_use()
+        self.calls["aph_reduce"] += 1
+        _lib.check(self.lib.phgpu_aph_reduce(self.h, 1 if first else 0, _ptr(mask), _ptr(self.x), _ptr(Wu), _ptr(zu),
+                                             _ptr(self.rho),
+                                             _ptr(self.aph_y), _ptr(self.aph_planes), self._stream()),
+                   "phgpu_aph_reduce")
+        if self.comm.size > 1:
+            self.calls["allreduce_aph_planes"] += 1
+        self._allreduce_sum_(self.aph_planes)
+
+    def aph_norms(self, gamma):
+        """x̄, u, phi and the second reduction (phgpu_aph_norms, aph.py:254-310): ``aph_red`` =
+        the ranks' sums of {tau, phi, p|u|², p|ȳ|², p W², p z²}, the last two being the local
+        sums of the previous phgpu_aph_update, as the reference sends them.  Device work only."""
+        self.calls["aph_norms"] += 1
+        _lib.check(self.lib.phgpu_aph_norms(self.h, float(gamma), _ptr(self.aph_planes), _ptr(self.x),
+                                            _ptr(self.aph_y), _ptr(self.W), _ptr(self.aph_z), _ptr(self.xbar),
+                                            _ptr(self.aph_u), _ptr(self.aph_phi), _ptr(self.aph_red), self._stream()),
+                   "phgpu_aph_norms")
+        self.aph_red[4:6].copy_(self.aph_out[0:2], non_blocking=True)
+        if self.comm.size > 1:
+            self.calls["allreduce_aph_scalars"] += 1
+        self._allreduce_sum_(self.aph_red)
+
+    def aph_update(self, first, nu, gamma):
+        """theta, W, z and the post-step phi (phgpu_aph_update, aph.py:453-496, 756); its four
+        scalars go to the pinned ``aph_out`` (``aph_scalars`` waits for them).  Device work only."""
+        self.calls["aph_update"] += 1
+        _lib.check(self.lib.phgpu_aph_update(self.h, 1 if first else 0, float(nu), float(gamma), _ptr(self.aph_red),
+                                             _ptr(self.aph_planes), _ptr(self.x), _ptr(self.aph_y), _ptr(self.aph_u),
+                                             _ptr(self.W), _ptr(self.aph_z), _ptr(self.aph_phi), _ptr(self.aph_out),
+                                             self._stream()), "phgpu_aph_update")
+        self._aph_red_host.copy_(self.aph_red, non_blocking=True)
+        self._aph_ev.record()
+
+    def aph_scalars(self):
+        """(sum p W², sum p z², theta, sum phi) of the last aph_update over the local scenarios
+        and the reduced ``aph_red`` as a host array: one wait and a read of pinned memory, the
+        iteration's one read."""
+        self.calls["aph_scalars_read"] += 1
+        self._aph_ev.synchronize()
+        o = self._aph_out_np
+        return (float(o[0]), float(o[1]), float(o[2]), float(o[3])), self._aph_red_host.numpy().copy()
+
+    def aph_mark(self, it, shelf_life, round_robin):
+        """The dispatch record of the scenarios in ``aph_mask`` and every scenario's next first
+        key (phgpu_aph_mark, aph.py:646, 529-550, 610-611, 626-629).  Device work only."""
+        self.calls["aph_mark"] += 1
+        _lib.check(self.lib.phgpu_aph_mark(self.h, _ptr(self.aph_mask), int(it), int(shelf_life),
+                                           1 if round_robin else 0, _ptr(self.aph_phi), _ptr(self.aph_last_iter),
+                                           _ptr(self.aph_last_phi), _ptr(self.aph_k1), _ptr(self.W), _ptr(self.aph_z),
+                                           _ptr(self.aph_W_lag), _ptr(self.aph_z_lag), self._stream()),
+                   "phgpu_aph_mark")
+
+    def select_smallest(self, k1, k2, count, mask=None, lst=None):
+        """Mark the ``count`` local scenarios smallest by (k1[s], k2[s], s) (phgpu_select_smallest):
+        ``mask`` int32 [S] of 0 / 1 and ``lst`` int32 [>= count] in ascending s (default: the
+        engine's ``aph_mask`` / ``aph_list``).  ``k1`` may be None.  Device work only."""
+        mask = self.aph_mask if mask is None else mask
+        lst = self.aph_list if lst is None else lst
+        self.calls["select_smallest"] = self.calls.get("select_smallest", 0) + 1
+        _lib.check(self.lib.phgpu_select_smallest(self.h, _ptr(k1), _ptr(k2), int(count), _ptr(mask), _ptr(lst),
+                                                  self._stream()), "phgpu_select_smallest")
+        return mask, lst
+
+    def solve_list(self, lst, count, options=None):
+        """A warm solve of the ``count`` scenarios in ``lst`` (device int32, ascending) in place
+        (phgpu_solve_list): their entries of the output tensors and of the warm-start state
+        are replaced, every other scenario's stay.  Returns the library's code for a
+        shared-matrix handle (-3), else 0."""
+        if getattr(self, "_xbar_pending", False):
+            self.compute_xbar()
+        o = options if options is not None else _lib.default_options()
+        self.calls["solve_list"] = self.calls.get("solve_list", 0) + 1
+        rc = self.lib.phgpu_solve_list(self.h, ctypes.byref(o), _ptr(lst), int(count), _ptr(self.x),
+                                       _ptr(self.y if self.want_duals else None), _ptr(self.obj), _ptr(self.bound),
+                                       _ptr(self.status), _ptr(self.iters), self._stream())
+        if rc == -3 and self.shared:
+            return rc
+        _lib.check(rc, "phgpu_solve_list")
+        if count > 0:
+            self._launch_id += 1
+            self._cur_id = self._launch_id
+            self._step_deferred = False
+        return 0
 
     def fix_nonants_by_node(self, table):
         """Fix every local scenario's nonants at per-node values: ``table`` is a device

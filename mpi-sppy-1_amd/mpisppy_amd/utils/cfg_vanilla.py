@@ -1,5 +1,5 @@
 """Cylinder dict builders (mirrors mpisppy/utils/cfg_vanilla.py:41-495 for the cylinders
-this engine serves: ph_hub, fwph_spoke, lagrangian_spoke, xhatshuffle_spoke, xhatxbar_spoke,
+this engine serves: ph_hub, aph_hub, fwph_spoke, lagrangian_spoke, xhatshuffle_spoke, xhatxbar_spoke,
 slammax_spoke, slammin_spoke; extension_adder, add_fixer and add_wxbar_read_write for the hub's
 extensions).
 
@@ -10,7 +10,7 @@ defaults.  The returned dicts feed ``WheelSpinner(hub_dict, list_of_spoke_dict)`
 import copy
 
 from ..cylinders.fwph_spoke import FrankWolfeOuterBound
-from ..cylinders.hub import PHHub
+from ..cylinders.hub import APHHub, PHHub
 from ..cylinders.lagrangian_bounder import LagrangianOuterBound
 from ..cylinders.slam_heuristic import SlamMaxHeuristic, SlamMinHeuristic
 from ..cylinders.xhatxbar_bounder import XhatXbarInnerBound
@@ -23,6 +23,7 @@ from ..extensions.gradient_extension import Gradient_extension
 from ..extensions.mult_rho_updater import MultRhoUpdater
 from ..extensions.norm_rho_updater import NormRhoUpdater
 from ..fwph.fwph import FWPH
+from ..opt.aph import APH
 from ..opt.ph import PH
 from ..phbase import PHBase
 from .xhat_eval import Xhat_Eval
@@ -84,6 +85,25 @@ def ph_hub(cfg, scenario_creator, scenario_denouement, all_scenario_names, scena
             "all_nodenames": all_nodenames,
         },
     }
+
+
+# cfg_vanilla.py:128-161
+def aph_hub(cfg, scenario_creator, scenario_denouement, all_scenario_names, scenario_creator_kwargs=None,
+            ph_extensions=None, extension_kwargs=None, rho_setter=None, variable_probability=None,
+            all_nodenames=None):
+    hub_dict = ph_hub(cfg, scenario_creator, scenario_denouement, all_scenario_names,
+                      scenario_creator_kwargs=scenario_creator_kwargs, ph_extensions=ph_extensions,
+                      extension_kwargs=extension_kwargs, rho_setter=rho_setter,
+                      variable_probability=variable_probability, all_nodenames=all_nodenames)
+    hub_dict["hub_class"] = APHHub
+    hub_dict["opt_class"] = APH
+    options = hub_dict["opt_kwargs"]["options"]
+    options["APHgamma"] = _get(cfg, "aph_gamma", 1.0)
+    options["APHnu"] = _get(cfg, "aph_nu", 1.0)
+    options["async_frac_needed"] = _get(cfg, "aph_frac_needed", 1.0)     # accepted and ignored (opt/aph.py)
+    options["dispatch_frac"] = _get(cfg, "aph_dispatch_frac", 1.0)
+    options["async_sleep_secs"] = _get(cfg, "aph_sleep_seconds", 0.01)   # accepted and ignored
+    return hub_dict
 
 
 # cfg_vanilla.py:277-317

@@ -18,6 +18,8 @@
  *                                          mpisppy/extensions/fixer.py:114-304 -> phgpu_fixer_step
  *   - FWPH's column set and QP per scenario (SDM, _add_QP_column, _conv_diff)
  *                                          mpisppy/fwph/fwph.py:210-370, 528-547 -> phgpu_fwph_*
+ *   - the L-shaped method's cuts and master LP
+ *                                          mpisppy/opt/lshaped.py:477-560, 600-630 -> phgpu_lshaped_*
  *   - APH's projective step, dispatch and partial solve loop (Update_y, Compute_Averages,
  *     listener_side_gig, Update_theta_zw, _dispatch_list, APH_solve_loop)
  *                                          mpisppy/opt/aph.py:151-195, 254-310, 394-408, 453-496,
@@ -687,6 +689,74 @@ int phgpu_select_smallest(phgpu_handle h, const double* k1, const double* k2, in
  * streaming kernel has no list mode yet); -1 before any solve (there is no warm state). */
 int phgpu_solve_list(phgpu_handle h, const phgpu_options* opt, const int32_t* list, int32_t count, double* x,
                      double* y, double* obj, double* bound, int32_t* status, int32_t* iters, void* stream);
+
+/* The L-shaped method (mpisppy/opt/lshaped.py), two-stage problems, minimisation: Benders cuts
+ * from the fixed solves of all local scenarios and the master LP, on the device.
+ *
+ *   master:  min sum_g eta_g  over x in R^nn (the ROOT nonants) and eta in R^G (one per cut group)
+ *            xlb <= x <= xub,  rl <= R x <= ru,  eta >= etalb,  eta_g - a.x >= b for every cut
+ *
+ * eta_g models sum_{s in g} prob_s f_s(x), f_s the whole objective of scenario s at first stage x;
+ * the scenario with global index s is in group s * G / S_total.  The reference keeps the master as
+ * a Pyomo model with one eta per scenario and hands it to an LP solver (lshaped.py:84-230,
+ * 600-630); it builds each cut from a scenario's duals in Python (:477-560).  All entries are
+ * ordered on the stream and give the same bits on every run; -3 on a PHGPU_SHARED_MATRIX handle
+ * and on a tree with more than two stages.
+ *
+ * phgpu_lshaped_init: allocate the cut store (max_cuts cuts of {group, a[nn], b}; the handle's,
+ * counted in phgpu_workspace_bytes, freed by phgpu_destroy or by another init) and take the
+ * master's data, all HOST arrays: R [n_rows][nn] dense first-stage rows with sides rl, ru (equal:
+ * an equality row), xlb, xub [nn] (infinite sides allowed; xlb < xub, a fixed column is refused with -1), etalb [G] (finite).
+ * s_off: the global index of local scenario 0; S_total: the scenarios of all ranks.
+ * Limits: nn <= 64, G <= 32, n_rows <= 64; beyond them -1 with a message. */
+int phgpu_lshaped_init(phgpu_handle h, int32_t G, int32_t max_cuts, int64_t s_off, int64_t S_total,
+                       int32_t n_rows, const double* R, const double* rl, const double* ru,
+                       const double* xlb, const double* xub, const double* etalb, void* stream);
+
+/* The cuts of one iteration (lshaped.py:477-520 for every scenario, then the groups' sums),
+ * before the ranks' sum.  x [n*S], y [m*S], obj [S], status [S]: the outputs of a solve with the
+ * nonants fixed (phgpu_fix_nonants), W off and prox off.  One lane per scenario forms the reduced
+ * cost of its fixed columns, d_k = c_k + q_k x_k - sum_i A_ik y_i; then one block per sum adds
+ * the scenarios' terms in a fixed order:
+ *   cutbuf [G * (nn + 2) + 1], device: per group a_g = sum p_s d_s [nn], b_g = sum p_s (obj_s -
+ *   d_s . x_s), Q_g = sum p_s obj_s; last the number of local scenarios that are not OPTIMAL
+ *   (they contribute nothing else).  All of it sums over the ranks (phgpu_allreduce_sum).
+ * The test of a cut against eta is phgpu_lshaped_append's, after that sum. */
+int phgpu_lshaped_cuts(phgpu_handle h, const double* x, const double* y, const double* obj,
+                       const int32_t* status, double* cutbuf, void* stream);
+
+/* Append the cuts that cut off eta (lshaped.py:540-560): group g gets {g, a_g, b_g} when
+ * Q_g - eta_g > tol max(1, |Q_g|), in group order; a full store takes no more.  eta [G] device.
+ *   info: double[5], device or host-mapped pinned memory, one store: {cuts added, sum_g Q_g (the
+ *   expected cost at the candidate), cuts held, scenarios not OPTIMAL, cuts wanted}.  wanted >
+ *   added means the store was full and cuts were dropped: the caller must not take "no cut
+ *   added" for convergence then. */
+int phgpu_lshaped_append(phgpu_handle h, const double* cutbuf, const double* eta, double tol,
+                         double* info, void* stream);
+
+/* Solve the master (the root solve of lshaped.py:600-630) as one workgroup: a dense fp64
+ * primal-dual interior point (Mehrotra's predictor-corrector, steps kept in the wide
+ * neighbourhood; the step only centres -- sigma = 1, no second-order term -- while the relative
+ * gap is below a tenth of eps_rel or below a tenth of the larger relative residual, so that the
+ * gap never runs ahead of the residuals) on the (nn + G)^2 normal matrix in LDS with a Cholesky factor; equality rows by a
+ * Schur complement on that factor; diagonal regularisation 1e-13 of each column's own diagonal
+ * (1e-10 on an x column without a finite bound).  At most 200 iterations.  opt: eps_rel (primal,
+ * dual and gap, relative) and eps_infeas are read; NULL: the defaults.  It starts from the
+ * previous master's solution (the store's warm state), the first time from xhat's scenario 0.
+ *   xhat [nn*S] device: the solution broadcast to every local scenario (what phgpu_fix_nonants takes);
+ *   eta [G] device;  info: double[6], device or host-mapped: {objective (the outer bound), status
+ *   (PHGPU_OPTIMAL, PHGPU_ITER_LIMIT, PHGPU_PRIMAL_INFEASIBLE when a Farkas ray was found),
+ *   iterations, primal, dual, gap residual}. */
+int phgpu_lshaped_master(phgpu_handle h, const phgpu_options* opt, double* xhat, double* eta,
+                         double* info, void* stream);
+
+/* The store from and to HOST arrays (tests, checkpoints); both synchronise the stream.
+ * load: K <= max_cuts cuts as group [K], a [K][nn], b [K]; it forgets the master's warm state.
+ * export: *ncuts and, where not NULL, group, a, b of the cuts held (room for max_cuts). */
+int phgpu_lshaped_load(phgpu_handle h, int32_t K, const int32_t* group, const double* a,
+                       const double* b, void* stream);
+int phgpu_lshaped_export(phgpu_handle h, int32_t* ncuts, int32_t* group, double* a, double* b,
+                         void* stream);
 
 /* Free the workspace and the handle. */
 int phgpu_destroy(phgpu_handle h);

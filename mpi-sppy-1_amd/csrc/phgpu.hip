@@ -23,6 +23,8 @@
 //                                       extensions/gradient_extension.py:65-95
 //   APH's projective step, dispatch and partial solve loop
 //                                       opt/aph.py:151-195, 254-310, 394-408, 453-496, 602-668
+//   the L-shaped method's cuts and master LP
+//                                       opt/lshaped.py:477-560, 600-666
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -72,6 +74,7 @@ struct jit_module;  // solve_jit.inc: the hipRTC-compiled path-5 kernel of a han
 struct ipm_module;  // solve_ipm.inc: the hipRTC-compiled path-6 module of a handle
 struct fwph_store;  // ph_fwph.inc: the FWPH column store of a handle
 struct sel_state;   // ph_aph.inc: the workspace of phgpu_select_smallest
+struct ls_store;    // ph_lshaped.inc: the cut store and master of the L-shaped method
 struct ph_ws {      // a reduction's device workspace: partials, and node tags or a ticket counter
     double* part;
     int32_t* tag;
@@ -260,6 +263,9 @@ struct phgpu_state {
     ph_ws apr, apn, apu;
     sel_state* sel;
     int32_t* list_n;
+    // phgpu_lshaped_*: the cut store, the master's data and work space (host record of its
+    // device buffers; null until phgpu_lshaped_init)
+    ls_store* ls;
 };
 
 // ------------------------------------------------------------------ ownership (host)
@@ -1117,6 +1123,7 @@ __global__ void k_stats_copy(const unsigned long long* __restrict__ src, int cop
 #include "ph_fixer.inc"
 #include "ph_fwph.inc"
 #include "ph_aph.inc"
+#include "ph_lshaped.inc"
 
 // Xhat_Eval._fix_nonants (utils/xhat_eval.py; spopt.py _fix_nonants): nonant columns of
 // every scenario get lb = ub = xfix[k, s] (scaled); xfix == NULL restores the model bounds.
@@ -3235,6 +3242,202 @@ extern "C" int phgpu_solve_list(phgpu_handle h, const phgpu_options* opt, const 
     return 0;
 }
 
+// ------------------------------------------------------------------ the L-shaped method (ph_lshaped.inc)
+static void lshaped_release(phgpu_state* h) {
+    ls_store* L = h->ls;
+    if (!L) return;
+    dfree(h, &L->cut_a); dfree(h, &L->cut_b); dfree(h, &L->cut_g); dfree(h, &L->ncuts);
+    dfree(h, &L->R); dfree(h, &L->rl); dfree(h, &L->ru); dfree(h, &L->eq);
+    dfree(h, &L->xlb); dfree(h, &L->xub); dfree(h, &L->etalb);
+    dfree(h, &L->zw); dfree(h, &L->has_w);
+    dfree(h, &L->s); dfree(h, &L->lam); dfree(h, &L->rp); dfree(h, &L->ds); dfree(h, &L->dl);
+    dfree(h, &L->t); dfree(h, &L->w); dfree(h, &L->V); dfree(h, &L->terms);
+    delete L;
+    h->ls = nullptr;
+}
+
+template <typename T>
+static int ls_upload(phgpu_state* h, T** d, const T* src, size_t count) {
+    const int rc = dalloc(h, d, count);
+    if (rc) return rc;
+    if (count && src) HIPCHK(hipMemcpy(*d, src, count * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// lshaped.py:84-160 (the root problem without its cuts) and the cut store
+extern "C" int phgpu_lshaped_init(phgpu_handle h, int32_t G, int32_t max_cuts, int64_t s_off, int64_t S_total,
+                                  int32_t n_rows, const double* R, const double* rl, const double* ru,
+                                  const double* xlb, const double* xub, const double* etalb, void* stream) {
+    if (!h) return set_err(-1, "null handle");
+    if (!h->scen_set) return set_err(-1, "phgpu_lshaped_init: no scenario data yet");
+    if (h->shared) return set_err(-3, "phgpu_lshaped_init: a shared-matrix handle is not served");
+    if (h->depth != 1 || h->num_nodes != 1)
+        return set_err(-3, "phgpu_lshaped_init: two-stage handles only (depth %d, %d nodes)", h->depth, h->num_nodes);
+    if (h->nn < 1 || h->nn > LS_NN_MAX || G < 1 || G > LS_G_MAX || n_rows < 0 || n_rows > LS_ROWS_MAX)
+        return set_err(-1, "phgpu_lshaped_init: nn %d (1..%d), G %d (1..%d), n_rows %d (0..%d)", h->nn, LS_NN_MAX, (int)G,
+                       LS_G_MAX, (int)n_rows, LS_ROWS_MAX);
+    if (max_cuts < 1 || max_cuts > (1 << 20)) return set_err(-1, "phgpu_lshaped_init: max_cuts %d", (int)max_cuts);
+    if (S_total < 1 || s_off < 0 || s_off + h->S > S_total)
+        return set_err(-1, "phgpu_lshaped_init: scenarios [%lld, %lld) of %lld", (long long)s_off,
+                       (long long)(s_off + h->S), (long long)S_total);
+    if (!xlb || !xub || !etalb || (n_rows && (!R || !rl || !ru))) return set_err(-1, "null argument");
+    const int nn = h->nn;
+    std::vector<int32_t> eq;
+    for (int k = 0; k < nn; ++k)
+        if (!(xlb[k] < xub[k]) || xlb[k] == INFINITY || xub[k] == -INFINITY)
+            return set_err(-1, "phgpu_lshaped_init: nonant %d has bounds [%g, %g] (no interior)", k, xlb[k], xub[k]);
+    for (int g = 0; g < G; ++g)
+        if (!isfinite(etalb[g])) return set_err(-1, "phgpu_lshaped_init: etalb[%d] = %g is not finite", g, etalb[g]);
+    for (int r = 0; r < n_rows; ++r) {
+        if (rl[r] > ru[r] || rl[r] == INFINITY || ru[r] == -INFINITY || rl[r] != rl[r] || ru[r] != ru[r])
+            return set_err(-1, "phgpu_lshaped_init: row %d has sides [%g, %g]", r, rl[r], ru[r]);
+        if (rl[r] == ru[r]) eq.push_back(r);
+    }
+    FLUSH_STEP(h);
+    hipStream_t st = (hipStream_t)stream;
+    if (h->ls) {
+        HIPCHK(hipStreamSynchronize(st));  // (nothing of the old store may be in flight)
+        lshaped_release(h);
+    }
+    ls_store* L = new (std::nothrow) ls_store();
+    if (!L) return set_err(-3, "out of host memory");
+    memset(L, 0, sizeof(*L));
+    h->ls = L;
+    L->G = G; L->nn = nn; L->N = nn + G; L->ld = (nn + G) | 1; L->max_cuts = max_cuts; L->n_rows = n_rows;
+    L->ne = (int)eq.size();
+    L->NI = 2 * nn + G + 2 * n_rows + max_cuts;
+    L->s_off = s_off; L->S_total = S_total;
+    const size_t NI = (size_t)L->NI, S = (size_t)h->S;
+    int rc = dalloc(h, &L->cut_a, (size_t)nn * max_cuts);
+    if (!rc) rc = dalloc(h, &L->cut_b, (size_t)max_cuts);
+    if (!rc) rc = dalloc(h, &L->cut_g, (size_t)max_cuts);
+    if (!rc) rc = dalloc(h, &L->ncuts, 1);
+    if (!rc) rc = ls_upload(h, &L->R, R, (size_t)n_rows * nn);
+    if (!rc) rc = ls_upload(h, &L->rl, rl, (size_t)n_rows);
+    if (!rc) rc = ls_upload(h, &L->ru, ru, (size_t)n_rows);
+    if (!rc) rc = ls_upload(h, &L->eq, eq.data(), eq.size());
+    if (!rc) rc = ls_upload(h, &L->xlb, xlb, (size_t)nn);
+    if (!rc) rc = ls_upload(h, &L->xub, xub, (size_t)nn);
+    if (!rc) rc = ls_upload(h, &L->etalb, etalb, (size_t)G);
+    if (!rc) rc = dalloc(h, &L->zw, (size_t)L->N);
+    if (!rc) rc = dalloc(h, &L->has_w, 1);
+    if (!rc) rc = dalloc(h, &L->s, NI);
+    if (!rc) rc = dalloc(h, &L->lam, NI);
+    if (!rc) rc = dalloc(h, &L->rp, NI);
+    if (!rc) rc = dalloc(h, &L->ds, NI);
+    if (!rc) rc = dalloc(h, &L->dl, NI);
+    if (!rc) rc = dalloc(h, &L->t, NI);
+    if (!rc) rc = dalloc(h, &L->w, NI);
+    if (!rc) rc = dalloc(h, &L->V, (size_t)L->N * std::max(1, L->ne));
+    if (!rc) rc = dalloc(h, &L->terms, (size_t)(nn + 3) * S);
+    if (rc) {
+        lshaped_release(h);
+        return rc;
+    }
+    HIPCHK(hipMemsetAsync(L->cut_a, 0, (size_t)nn * max_cuts * sizeof(double), st));
+    HIPCHK(hipMemsetAsync(L->cut_b, 0, (size_t)max_cuts * sizeof(double), st));
+    HIPCHK(hipMemsetAsync(L->cut_g, 0, (size_t)max_cuts * sizeof(int32_t), st));
+    HIPCHK(hipMemsetAsync(L->ncuts, 0, sizeof(int32_t), st));
+    HIPCHK(hipMemsetAsync(L->has_w, 0, sizeof(int32_t), st));
+    HIPCHK(hipMemsetAsync(L->zw, 0, (size_t)L->N * sizeof(double), st));
+    return 0;
+}
+
+#define LSHAPED_READY(h, who)                                                       \
+    do {                                                                            \
+        if (!(h)) return set_err(-1, "null handle");                                \
+        if (!(h)->ls) return set_err(-1, who ": phgpu_lshaped_init has not run");  \
+        FLUSH_STEP(h);                                                              \
+    } while (0)
+
+// lshaped.py:477-520, all local scenarios and their group sums
+extern "C" int phgpu_lshaped_cuts(phgpu_handle h, const double* x, const double* y, const double* obj,
+                                  const int32_t* status, double* cutbuf, void* stream) {
+    LSHAPED_READY(h, "phgpu_lshaped_cuts");
+    if (!x || !y || !obj || !status || !cutbuf) return set_err(-1, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    const ls_store& L = *h->ls;
+    hipLaunchKernelGGL(k_ls_terms, dim3((unsigned)((h->S + GR_T - 1) / GR_T)), dim3(GR_T), 0, st, *h, L, x, y, obj,
+                       status);
+    hipLaunchKernelGGL(k_ls_gsum, dim3((unsigned)(L.G * (L.nn + 2) + 1)), dim3(GR_T), 0, st, L, h->S, cutbuf);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// lshaped.py:540-560
+extern "C" int phgpu_lshaped_append(phgpu_handle h, const double* cutbuf, const double* eta, double tol, double* info,
+                                    void* stream) {
+    LSHAPED_READY(h, "phgpu_lshaped_append");
+    if (!cutbuf || !eta || !info) return set_err(-1, "null argument");
+    if (!(tol >= 0.0)) return set_err(-1, "phgpu_lshaped_append: tol %g", tol);
+    hipLaunchKernelGGL(k_ls_append, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, *h->ls, cutbuf, eta, tol, info);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// lshaped.py:600-630 (the root solve)
+extern "C" int phgpu_lshaped_master(phgpu_handle h, const phgpu_options* opt, double* xhat, double* eta, double* info,
+                                    void* stream) {
+    LSHAPED_READY(h, "phgpu_lshaped_master");
+    if (!xhat || !eta || !info) return set_err(-1, "null argument");
+    phgpu_options o;
+    if (opt) o = *opt;
+    else phgpu_default_options(&o);
+    if (!(o.eps_rel > 0.0) || !(o.eps_infeas > 0.0))
+        return set_err(-1, "phgpu_lshaped_master: eps_rel %g, eps_infeas %g", o.eps_rel, o.eps_infeas);
+    const ls_store& L = *h->ls;
+    const size_t lds = ls_shared_doubles(L.N, L.ld, L.ne) * sizeof(double);
+    if (lds > (size_t)160 * 1024) return set_err(-3, "phgpu_lshaped_master: %zu bytes of LDS", lds);
+    HIPCHK(hipFuncSetAttribute((const void*)k_ls_master, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_ls_master, dim3(1), dim3(LS_T), lds, (hipStream_t)stream, L, h->S, o.eps_rel, o.eps_infeas,
+                       LS_ITER_CAP, xhat, eta, info);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// the store from / to the host (tests, checkpoints): K cuts as group [K], a [K][nn], b [K]
+extern "C" int phgpu_lshaped_load(phgpu_handle h, int32_t K, const int32_t* group, const double* a, const double* b,
+                                  void* stream) {
+    LSHAPED_READY(h, "phgpu_lshaped_load");
+    ls_store& L = *h->ls;
+    if (K < 0 || K > L.max_cuts) return set_err(-1, "phgpu_lshaped_load: %d cuts, the store holds %d", (int)K, L.max_cuts);
+    if (K && (!group || !a || !b)) return set_err(-1, "null argument");
+    for (int c = 0; c < K; ++c)
+        if (group[c] < 0 || group[c] >= L.G) return set_err(-1, "phgpu_lshaped_load: cut %d in group %d", c, (int)group[c]);
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<double> at((size_t)L.nn * L.max_cuts, 0.0);
+    for (int c = 0; c < K; ++c)
+        for (int k = 0; k < L.nn; ++k) at[(size_t)k * L.max_cuts + c] = a[(size_t)c * L.nn + k];
+    HIPCHK(hipMemcpy(L.cut_a, at.data(), at.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (K) HIPCHK(hipMemcpy(L.cut_b, b, (size_t)K * sizeof(double), hipMemcpyHostToDevice));
+    if (K) HIPCHK(hipMemcpy(L.cut_g, group, (size_t)K * sizeof(int32_t), hipMemcpyHostToDevice));
+    const int32_t k32 = K, zero = 0;
+    HIPCHK(hipMemcpy(L.ncuts, &k32, sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(L.has_w, &zero, sizeof(int32_t), hipMemcpyHostToDevice));
+    return 0;
+}
+
+extern "C" int phgpu_lshaped_export(phgpu_handle h, int32_t* ncuts, int32_t* group, double* a, double* b, void* stream) {
+    LSHAPED_READY(h, "phgpu_lshaped_export");
+    if (!ncuts) return set_err(-1, "null argument");
+    ls_store& L = *h->ls;
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    int32_t K = 0;
+    HIPCHK(hipMemcpy(&K, L.ncuts, sizeof(int32_t), hipMemcpyDeviceToHost));
+    K = std::min(K, (int32_t)L.max_cuts);
+    *ncuts = K;
+    if (K && group) HIPCHK(hipMemcpy(group, L.cut_g, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (K && b) HIPCHK(hipMemcpy(b, L.cut_b, (size_t)K * sizeof(double), hipMemcpyDeviceToHost));
+    if (K && a) {
+        std::vector<double> at((size_t)L.nn * L.max_cuts);
+        HIPCHK(hipMemcpy(at.data(), L.cut_a, at.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (int c = 0; c < K; ++c)
+            for (int k = 0; k < L.nn; ++k) a[(size_t)c * L.nn + k] = at[(size_t)k * L.max_cuts + c];
+    }
+    return 0;
+}
+
 #include "comm_rccl.inc"
 
 extern "C" int phgpu_destroy(phgpu_handle h) {
@@ -3244,6 +3447,7 @@ extern "C" int phgpu_destroy(phgpu_handle h) {
     module_release(h->ipm);
     module_release(h->ipm_loop);
     delete h->fw;  // (its device buffers are in allocs)
+    delete h->ls;
     phgpu_owner* o = owner_of(h);  // (a deferred step that never ran is dropped with it)
     for (const dev_alloc& a : o->allocs) (void)hipFree(a.p);
     delete o;

@@ -86,7 +86,9 @@ EXPORTS = ["phgpu_default_options", "phgpu_create", "phgpu_create2", "phgpu_set_
            "phgpu_fwph_init", "phgpu_fwph_load", "phgpu_fwph_export", "phgpu_fwph_direction",
            "phgpu_fwph_column", "phgpu_fwph_diff",
            "phgpu_aph_reduce", "phgpu_aph_norms", "phgpu_aph_update", "phgpu_aph_mark",
-           "phgpu_select_smallest", "phgpu_solve_list"]
+           "phgpu_select_smallest", "phgpu_solve_list",
+           "phgpu_lshaped_init", "phgpu_lshaped_cuts", "phgpu_lshaped_append", "phgpu_lshaped_master",
+           "phgpu_lshaped_load", "phgpu_lshaped_export"]
 
 _lib = None
 
@@ -157,6 +159,12 @@ def load(path=None):
     lib.phgpu_aph_mark.argtypes = [c_vp, c_vp, c_i32, c_i32, c_int] + [c_vp] * 9
     lib.phgpu_select_smallest.argtypes = [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]
     lib.phgpu_solve_list.argtypes = [c_vp, ctypes.POINTER(PhgpuOptions), c_vp, c_i32] + [c_vp] * 7
+    lib.phgpu_lshaped_init.argtypes = [c_vp, c_i32, c_i32, c_i64, c_i64, c_i32] + [c_vp] * 7
+    lib.phgpu_lshaped_cuts.argtypes = [c_vp] + [c_vp] * 6
+    lib.phgpu_lshaped_append.argtypes = [c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp]
+    lib.phgpu_lshaped_master.argtypes = [c_vp, ctypes.POINTER(PhgpuOptions), c_vp, c_vp, c_vp, c_vp]
+    lib.phgpu_lshaped_load.argtypes = [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]
+    lib.phgpu_lshaped_export.argtypes = [c_vp, P_i32, c_vp, c_vp, c_vp, c_vp]
     lib.phgpu_ipm_info.argtypes = [c_vp, ctypes.POINTER(c_dbl)]
     lib.phgpu_ipm_prof.argtypes = [c_vp, ctypes.POINTER(ctypes.c_ulonglong), c_i64]
     lib.phgpu_ipm_prof.restype = c_i64

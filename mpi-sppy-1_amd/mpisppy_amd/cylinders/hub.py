@@ -383,3 +383,68 @@ class APHHub(PHHub):
 
     def main(self):
         self.opt.APH_main(spcomm=self, finalize=False)
+
+
+class LShapedHub(PHHub):
+    """The hub of the L-shaped method (reference hub.py:600-689): the candidate x̂ out to the
+    nonant spokes, the bounds in, and the master's objective folded into the outer bound."""
+
+    # hub.py:602-640
+    def setup_hub(self):
+        self.initialize_spoke_indices()
+        if self.has_w_spokes:
+            raise RuntimeError("LShaped hub does not compute dual weights (Ws)")
+        super().setup_hub()
+
+    # hub.py:642-659
+    def sync(self, send_nonants=True):
+        self._hub_write_id += 1
+        if self.layout is not None:
+            self.serve_spokes()
+        else:
+            if send_nonants and self.has_nonant_spokes:
+                self.send_nonants()
+            self.run_spokes()
+        if self.has_outerbound_spokes:
+            self.receive_outerbounds()
+        if self.has_innerbound_spokes:
+            self.receive_innerbounds()
+
+    # hub.py:661-676
+    def is_converged(self):
+        self.BestOuterBound = self.OuterBoundUpdate(self.opt._LShaped_bound)
+        if not self.has_innerbound_spokes:
+            if self.opt.iter == 0:
+                logger.warning("LShapedHub cannot compute convergence without inner bound spokes.")
+            if self.global_rank == 0:
+                self.screen_trace()
+            return False
+        if self.global_rank == 0:
+            self.screen_trace()
+        return self.determine_termination()
+
+    def current_iteration(self):
+        return self.opt.iter
+
+    def main(self):
+        self.opt.lshaped_algorithm()
+
+    def _window_values(self, idx):
+        if idx in self.nonant_spoke_indices:
+            return self.opt.nonants_dev()
+        return None
+
+    def send_terminate(self):
+        Hub.send_terminate(self)
+
+    def finalize(self):
+        return None
+
+    # hub.py:678-689 (the root variables' values, for every local scenario)
+    def send_nonants(self):
+        x = self.opt.nonants_dev()
+        if self._nonant_snapshot is None:
+            self._nonant_snapshot = torch.empty_like(x)
+        self._nonant_snapshot.copy_(x)
+        for idx in self.nonant_spoke_indices:
+            self.hub_to_spoke(self._nonant_snapshot, idx)

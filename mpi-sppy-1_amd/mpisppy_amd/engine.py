@@ -1382,6 +1382,97 @@ class PHEngine:
             self._step_deferred = False
         return 0
 
+    # -------------------------------------------------------------- L-shaped
+    def lshaped_init(self, G, max_cuts, s_off, S_total, R, rl, ru, xlb, xub, etalb):
+        """The cut store and the master's data (phgpu_lshaped_init; lshaped.py:84-230): host
+        arrays R [n_rows, nn], rl, ru, xlb, xub [nn], etalb [G].  Buffers: ``ls_xhat`` [nn, S]
+        (the candidate, what ``fix_nonants`` takes), ``ls_eta`` [G], ``ls_cutbuf`` and the pinned
+        ``ls_info`` (12 doubles: phgpu_lshaped_append's 5 at 0, phgpu_lshaped_master's 6 at 6)."""
+        self._flush_step()
+        f8 = lambda a, shape: np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(shape))  # noqa: E731
+        nn, G = self.nn, int(G)
+        rl, ru = f8(rl, (-1,)), f8(ru, (-1,))
+        n_rows = len(rl)
+        R = f8(R, (n_rows, nn))
+        xlb, xub, etalb = f8(xlb, (nn,)), f8(xub, (nn,)), f8(etalb, (G,))
+        hp = lambda a: ctypes.c_void_p(a.ctypes.data) if a.size else None  # noqa: E731
+        _lib.check(self.lib.phgpu_lshaped_init(self.h, G, int(max_cuts), int(s_off), int(S_total), n_rows, hp(R),
+                                               hp(rl), hp(ru), hp(xlb), hp(xub), hp(etalb), self._stream()),
+                   "phgpu_lshaped_init")
+        self.ls_G, self.ls_max_cuts = G, int(max_cuts)
+        z = lambda *s: torch.zeros(*s, dtype=torch.float64, device=self.device)  # noqa: E731
+        self.ls_xhat = z(max(nn, 1), self.S)
+        self.ls_eta = torch.from_numpy(etalb).to(self.device)
+        self.ls_cutbuf = z(G * (nn + 2) + 1)
+        self.ls_info = torch.zeros(12, dtype=torch.float64).pin_memory()
+        self._ls_info_np = self.ls_info.numpy()
+        self._ls_ev = torch.cuda.Event()
+        for k in ("lshaped_cuts", "lshaped_append", "lshaped_master", "allreduce_cuts"):
+            self.calls[k] = 0
+
+    def lshaped_cuts(self):
+        """The groups' cut sums of the last (fixed) solve into ``ls_cutbuf``, summed over the
+        ranks (phgpu_lshaped_cuts; lshaped.py:477-520).  The solve must have filled ``y``
+        (``want_duals``).  Device work only."""
+        self.calls["lshaped_cuts"] += 1
+        _lib.check(self.lib.phgpu_lshaped_cuts(self.h, _ptr(self.x), _ptr(self.y), _ptr(self.obj), _ptr(self.status),
+                                               _ptr(self.ls_cutbuf), self._stream()), "phgpu_lshaped_cuts")
+        if self.comm.size > 1:
+            self.calls["allreduce_cuts"] += 1
+            self._ar(self.ls_cutbuf)
+
+    def lshaped_append(self, tol):
+        """Append the cuts that cut off ``ls_eta`` (phgpu_lshaped_append; lshaped.py:540-560);
+        its five numbers go to ``ls_info[0:5]``.  Device work only."""
+        self.calls["lshaped_append"] += 1
+        self._ls_info_np[:5] = np.nan
+        _lib.check(self.lib.phgpu_lshaped_append(self.h, _ptr(self.ls_cutbuf), _ptr(self.ls_eta), float(tol),
+                                                 ctypes.c_void_p(self.ls_info.data_ptr()), self._stream()),
+                   "phgpu_lshaped_append")
+        self._ls_ev.record()
+
+    def lshaped_master(self, options=None):
+        """Solve the master into ``ls_xhat`` and ``ls_eta`` (phgpu_lshaped_master; lshaped.py:
+        600-630); its six numbers go to ``ls_info[6:12]``.  Device work only."""
+        self.calls["lshaped_master"] += 1
+        self._ls_info_np[6:] = np.nan
+        o = options if options is not None else _lib.default_options()
+        _lib.check(self.lib.phgpu_lshaped_master(self.h, ctypes.byref(o), _ptr(self.ls_xhat), _ptr(self.ls_eta),
+                                                 ctypes.c_void_p(self.ls_info.data_ptr() + 48), self._stream()),
+                   "phgpu_lshaped_master")
+        self._ls_ev.record()
+
+    def lshaped_read(self):
+        """The iteration's one read: a wait for the last append / master and the pinned
+        ``ls_info`` as a dict."""
+        self._ls_ev.synchronize()
+        v = self._ls_info_np
+        return {"added": v[0], "Q": v[1], "held": v[2], "not_optimal": v[3], "wanted": v[4], "bound": v[6],
+                "status": v[7], "iters": v[8], "pres": v[9], "dres": v[10], "gap": v[11]}
+
+    def lshaped_load(self, group, a, b):
+        """Fill the store from host arrays (phgpu_lshaped_load): group [K], a [K, nn], b [K]."""
+        group = np.ascontiguousarray(group, dtype=np.int32)
+        K = len(group)
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(K, self.nn))
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        hp = lambda v: ctypes.c_void_p(v.ctypes.data) if v.size else None  # noqa: E731
+        _lib.check(self.lib.phgpu_lshaped_load(self.h, K, hp(group), hp(a), hp(b), self._stream()),
+                   "phgpu_lshaped_load")
+
+    def lshaped_export(self):
+        """The store on the host (phgpu_lshaped_export): (group [K], a [K, nn], b [K])."""
+        mc = self.ls_max_cuts
+        group = np.zeros(mc, dtype=np.int32)
+        a = np.zeros((mc, self.nn))
+        b = np.zeros(mc)
+        K = np.zeros(1, dtype=np.int32)
+        _lib.check(self.lib.phgpu_lshaped_export(self.h, K.ctypes.data_as(_lib.P_i32), ctypes.c_void_p(group.ctypes.data),
+                                                 ctypes.c_void_p(a.ctypes.data), ctypes.c_void_p(b.ctypes.data),
+                                                 self._stream()), "phgpu_lshaped_export")
+        K = int(K[0])
+        return group[:K], a[:K], b[:K]
+
     def fix_nonants_by_node(self, table):
         """Fix every local scenario's nonants at per-node values: ``table`` is a device
         [num_nodes, nlen_max] tensor (global node order of ``node_names``); nonant k of

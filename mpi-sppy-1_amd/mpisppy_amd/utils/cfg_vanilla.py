@@ -1,6 +1,6 @@
 """Cylinder dict builders (mirrors mpisppy/utils/cfg_vanilla.py:41-495 for the cylinders
-this engine serves: ph_hub, aph_hub, fwph_spoke, lagrangian_spoke, xhatshuffle_spoke, xhatxbar_spoke,
-slammax_spoke, slammin_spoke; extension_adder, add_fixer and add_wxbar_read_write for the hub's
+this engine serves: ph_hub, aph_hub, lshaped_hub, fwph_spoke, lagrangian_spoke, xhatshuffle_spoke, xhatxbar_spoke,
+xhatlshaped_spoke, slammax_spoke, slammin_spoke; extension_adder, add_fixer and add_wxbar_read_write for the hub's
 extensions).
 
 ``cfg`` is any object with the reference's config attribute names (solver_name,
@@ -10,8 +10,9 @@ defaults.  The returned dicts feed ``WheelSpinner(hub_dict, list_of_spoke_dict)`
 import copy
 
 from ..cylinders.fwph_spoke import FrankWolfeOuterBound
-from ..cylinders.hub import APHHub, PHHub
+from ..cylinders.hub import APHHub, LShapedHub, PHHub
 from ..cylinders.lagrangian_bounder import LagrangianOuterBound
+from ..cylinders.lshaped_bounder import XhatLShapedInnerBound
 from ..cylinders.slam_heuristic import SlamMaxHeuristic, SlamMinHeuristic
 from ..cylinders.xhatxbar_bounder import XhatXbarInnerBound
 from ..cylinders.xhatshufflelooper_bounder import XhatShuffleInnerBound
@@ -24,6 +25,7 @@ from ..extensions.mult_rho_updater import MultRhoUpdater
 from ..extensions.norm_rho_updater import NormRhoUpdater
 from ..fwph.fwph import FWPH
 from ..opt.aph import APH
+from ..opt.lshaped import LShapedMethod
 from ..opt.ph import PH
 from ..phbase import PHBase
 from .xhat_eval import Xhat_Eval
@@ -214,6 +216,63 @@ def xhatxbar_spoke(cfg, scenario_creator, scenario_denouement, all_scenario_name
             "scenario_denouement": scenario_denouement,
             "variable_probability": variable_probability,
             "all_nodenames": all_nodenames,
+        },
+    }
+
+
+# this project's convenience, as aph_hub (the reference builds the dict by hand,
+# examples/farmer/farmer_lshapedhub.py:60-85)
+def lshaped_hub(cfg, scenario_creator, scenario_denouement, all_scenario_names, scenario_creator_kwargs=None,
+                all_nodenames=None):
+    sh = shared_options(cfg)
+    options = {
+        "root_solver": sh["solver_name"],
+        "sp_solver": sh["solver_name"],
+        "solver_name": sh["solver_name"],
+        "root_solver_options": dict(_get(cfg, "root_solver_options", {})),
+        "sp_solver_options": dict(sh["iterk_solver_options"]),
+        "max_iter": _get(cfg, "max_iterations", 30),
+        "tol": _get(cfg, "lshaped_tol", None),
+        "cut_groups": getattr(cfg, "cut_groups", None),
+        "valid_eta_lb": getattr(cfg, "valid_eta_lb", None),
+        "verbose": sh["verbose"],
+        "device": sh["device"],
+        "toc": sh["toc"],
+    }
+    if options["tol"] is None:
+        del options["tol"]
+    if "batch_creator" in sh:
+        options["batch_creator"] = sh["batch_creator"]
+    return {
+        "hub_class": LShapedHub,
+        "hub_kwargs": {"options": {"rel_gap": getattr(cfg, "rel_gap", None),
+                                   "abs_gap": getattr(cfg, "abs_gap", None),
+                                   "max_stalled_iters": getattr(cfg, "max_stalled_iters", None)}},
+        "opt_class": LShapedMethod,
+        "opt_kwargs": {
+            "options": options,
+            "all_scenario_names": all_scenario_names,
+            "scenario_creator": scenario_creator,
+            "scenario_creator_kwargs": scenario_creator_kwargs,
+            "scenario_denouement": scenario_denouement,
+            "all_nodenames": all_nodenames,
+        },
+    }
+
+
+# cfg_vanilla.py:529-552
+def xhatlshaped_spoke(cfg, scenario_creator, scenario_denouement, all_scenario_names, scenario_creator_kwargs=None):
+    xhat_options = copy.deepcopy(shared_options(cfg))
+    xhat_options["bundles_per_rank"] = 0
+    return {
+        "spoke_class": XhatLShapedInnerBound,
+        "opt_class": Xhat_Eval,
+        "opt_kwargs": {
+            "options": xhat_options,
+            "all_scenario_names": all_scenario_names,
+            "scenario_creator": scenario_creator,
+            "scenario_creator_kwargs": scenario_creator_kwargs,
+            "scenario_denouement": scenario_denouement,
         },
     }
 

@@ -20,6 +20,8 @@
  *                                          mpisppy/fwph/fwph.py:210-370, 528-547 -> phgpu_fwph_*
  *   - the L-shaped method's cuts and master LP
  *                                          mpisppy/opt/lshaped.py:477-560, 600-630 -> phgpu_lshaped_*
+ *   - the per-batch moments of the MMW gap estimators and of zhat4xhat
+ *                                          mpisppy/confidence_intervals/ciutils.py:400-415 -> phgpu_gap_moments
  *   - APH's projective step, dispatch and partial solve loop (Update_y, Compute_Averages,
  *     listener_side_gig, Update_theta_zw, _dispatch_list, APH_solve_loop)
  *                                          mpisppy/opt/aph.py:151-195, 254-310, 394-408, 453-496,
@@ -447,6 +449,28 @@ int phgpu_rho_from_stats(phgpu_handle h, const double* planes, int64_t S_total, 
  *   xhatbase.py:210-216, is only taken when this equals E1) */
 int phgpu_expectations(phgpu_handle h, const double* obj, const double* bound,
                        const int32_t* status, double* out, void* stream);
+
+/* Per-segment moments of two batched solves: what the Mak-Morton-Wood gap estimator
+ * (confidence_intervals/ciutils.py:400-415) and zhat4xhat (zhat4xhat.py:94) take of the
+ * per-scenario objectives, reduced on the device.
+ *   f_hat, f_star: device [S], the objectives of the local scenarios in the two solves (at the
+ *   candidate and at the sample problem's optimum); st_hat, st_star: their status outputs.
+ *   f_star and st_star may both be NULL (no x* side: g and f_star count as 0, st_hat alone
+ *   decides what is left out); exactly one of them NULL is an error.
+ *   seg_ptr: device int64[nseg + 1], ascending, in GLOBAL scenario indices; local scenario k has
+ *   the global index s_off + k.  A segment may begin before the local scenarios, end behind
+ *   them, miss them or be empty; seg_ptr's contents are not validated.
+ *   out: device [nseg][8].  With p the handle's scenario probabilities and g = f_hat - f_star,
+ *   row j holds over the local scenarios of segment j
+ *     {sum p, sum p^2, sum p g, sum p g^2, sum p f_hat, sum p f_star, scenarios left out, 0};
+ *   a scenario that is not PHGPU_OPTIMAL in either solve is left out of the six sums and counted.
+ * The sums are made in a fixed order without atomics (two calls give the same bits) and are not
+ * normalised: the caller divides by sum p after summing the rows over the ranks.  The workspace
+ * (two slots of 7 partials per wave) is allocated at the first call. */
+int phgpu_gap_moments(phgpu_handle h, const double* f_hat, const int32_t* st_hat,
+                      const double* f_star, const int32_t* st_star,
+                      const int64_t* seg_ptr, int32_t nseg, int64_t s_off,
+                      double* out, void* stream);
 
 /* counts[c] = number of local scenarios whose status[s] == c, c = 0..3 (OPTIMAL,
  * ITER_LIMIT, PRIMAL_INFEASIBLE, DUAL_INFEASIBLE): the check behind SPOpt.solve_loop's

@@ -266,6 +266,9 @@ struct phgpu_state {
     // phgpu_lshaped_*: the cut store, the master's data and work space (host record of its
     // device buffers; null until phgpu_lshaped_init)
     ls_store* ls;
+    // phgpu_gap_moments: two slots of GM_NV partials per wave (its head and its tail run) and
+    // their segment tags [2 * nwaves], allocated at its first call
+    ph_ws gm;
 };
 
 // ------------------------------------------------------------------ ownership (host)
@@ -1124,6 +1127,7 @@ __global__ void k_stats_copy(const unsigned long long* __restrict__ src, int cop
 #include "ph_fwph.inc"
 #include "ph_aph.inc"
 #include "ph_lshaped.inc"
+#include "ph_gap.inc"
 
 // Xhat_Eval._fix_nonants (utils/xhat_eval.py; spopt.py _fix_nonants): nonant columns of
 // every scenario get lb = ub = xfix[k, s] (scaled); xfix == NULL restores the model bounds.
@@ -2855,6 +2859,30 @@ extern "C" int phgpu_expectations(phgpu_handle h, const double* obj, const doubl
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_sum_partials, dim3(5), dim3(256), 0, st, (const double*)h->part, h->nwaves, 5, 1.0,
                        out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// confidence_intervals/ciutils.py:400-415 (and zhat4xhat.py:94 with the x* side NULL)
+extern "C" int phgpu_gap_moments(phgpu_handle h, const double* f_hat, const int32_t* st_hat, const double* f_star,
+                                 const int32_t* st_star, const int64_t* seg_ptr, int32_t nseg, int64_t s_off,
+                                 double* out, void* stream) {
+    if (!h || !f_hat || !st_hat || !seg_ptr || !out) return set_err(-1, "null argument");
+    if (nseg < 1) return set_err(-1, "phgpu_gap_moments: nseg %d", (int)nseg);
+    if ((f_star == nullptr) != (st_star == nullptr))
+        return set_err(-1, "phgpu_gap_moments: f_star and st_star go together (both or neither)");
+    if (!h->scen_set) return set_err(-1, "phgpu_gap_moments: no scenario data yet");
+    FLUSH_STEP(h);
+    hipStream_t st = (hipStream_t)stream;
+    if (!h->gm.part) {
+        const int rc = ws_alloc(h, h->gm, (size_t)h->nwaves * 2 * GM_NV, (size_t)h->nwaves * 2);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_gap_partial, grid_for(h->S), dim3(BLOCK), 0, st, *h, f_hat, st_hat, f_star, st_star, seg_ptr,
+                       (int)nseg, s_off, h->gm.part, h->gm.tag, out);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_gap_final, dim3((unsigned)nseg), dim3(WAVE), 0, st, h->S, seg_ptr, s_off,
+                       (const double*)h->gm.part, (const int32_t*)h->gm.tag, out);
     HIPCHK(hipGetLastError());
     return 0;
 }

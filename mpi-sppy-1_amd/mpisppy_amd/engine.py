@@ -22,6 +22,7 @@ GPU, scenario-fastest ``[k, S]``) and sequences the per-PH-iteration work:
     APH             -> phgpu_aph_reduce + all-reduce, phgpu_aph_norms + all-reduce,
                        phgpu_aph_update, phgpu_select_smallest, phgpu_solve_list, phgpu_aph_mark
                                                        (opt/aph.py:151-195, 254-310, 453-496, 602-646)
+    gap estimators  -> phgpu_gap_moments + all-reduce  (confidence_intervals/ciutils.py:400-415)
 
 All launches go to torch's current stream; host synchronisation happens only where
 the reference needs a host scalar (the convergence test, bounds).
@@ -174,7 +175,9 @@ class PHEngine:
         self.conv_buf = z(1)
         self.exp_buf = z(5)
         self.xfix = None
-        self.pvar = None          # per-nonant probability coefficients (set_nonant_probs)
+        self.scen_offset = 0      # global index of local scenario 0 (SPOpt sets it; gap_moments)
+        self._gap_out = None
+        self.pvar = None        # per-nonant probability coefficients (set_nonant_probs)
         self.W_on = 0
         self.prox_on = 0
         # row duals are an optional phgpu_solve output: PH never reads them, so the hot
@@ -1048,6 +1051,27 @@ class PHEngine:
         self.comm.allreduce_sum_(self.exp_buf)
         v = self.exp_buf.cpu().numpy()
         return float(v[0]), float(v[1]), float(v[2]), float(v[3]), float(v[4])
+
+    def gap_moments(self, seg_ptr, f_hat, st_hat, f_star=None, st_star=None, s_off=None):
+        """Per-segment moments of two solves' objectives (phgpu_gap_moments; ciutils.py:400-415),
+        summed over the ranks: host [nseg, 8] rows {sum p, sum p^2, sum p g, sum p g^2, sum p f_hat,
+        sum p f_star, scenarios left out, 0} with g = f_hat - f_star.  ``seg_ptr``: nseg + 1
+        ascending global scenario indices; ``f_*`` / ``st_*``: device [S] objectives and statuses
+        (``f_star`` and ``st_star`` both None: the zhat4xhat form).  ``s_off``: the global index
+        of local scenario 0 (default ``self.scen_offset``, which SPOpt sets).  Reading the
+        result is the only synchronisation."""
+        sp = torch.as_tensor(np.asarray(seg_ptr, dtype=np.int64)).to(self.device) if not torch.is_tensor(seg_ptr) \
+            else seg_ptr.to(device=self.device, dtype=torch.int64).contiguous()
+        nseg = int(sp.numel()) - 1
+        if self._gap_out is None or self._gap_out.shape[0] != nseg:
+            self._gap_out = torch.zeros((max(nseg, 1), 8), dtype=torch.float64, device=self.device)
+        off = int(self.scen_offset if s_off is None else s_off)
+        self.calls["gap_moments"] = self.calls.get("gap_moments", 0) + 1
+        _lib.check(self.lib.phgpu_gap_moments(self.h, _ptr(f_hat), _ptr(st_hat), _ptr(f_star), _ptr(st_star),
+                                              _ptr(sp), nseg, off, _ptr(self._gap_out), self._stream()),
+                   "phgpu_gap_moments")
+        self.comm.allreduce_sum_(self._gap_out)
+        return self._gap_out.cpu().numpy()
 
     def fix_nonants(self, xfix):
         """lb = ub = xfix on the nonant columns of every local scenario (device [nn, S]

@@ -102,6 +102,7 @@ class SPOpt(SPBase):
         if self.engine is None:
             self.engine = PHEngine(self.batch, device=self.options.get("device"), comm=self.mpicomm,
                                    node_names=self.node_names, shared=self.options.get("shared_matrix"))
+            self.engine.scen_offset = int(self._rank_slices[self.cylinder_rank][0])
             if getattr(self, "var_prob", None) is not None:
                 self.engine.set_nonant_probs(self.var_prob)
             if self.options.get("ipm_tuning"):

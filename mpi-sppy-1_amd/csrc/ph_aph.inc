@@ -13,7 +13,7 @@
 // grid row: y = 0 with first, else W_use + rho (x - z_use) where mask is set (null: everywhere),
 // else kept; then the three sums per (wave, nonant) for k_node_final<0, 3>.
 __global__ void __launch_bounds__(BLOCK)
-k_aph_reduce_partial(phgpu_state st, ph_ws ws, int first, const int32_t* __restrict__ mask,
+k_aph_reduce_partial(ph_tree st, ph_ws ws, int first, const int32_t* __restrict__ mask,
                      const double* __restrict__ x, const double* __restrict__ Wu, const double* __restrict__ zu,
                      const double* __restrict__ rho, double* __restrict__ y, double* __restrict__ planes) {
     const int64_t S = st.S;
@@ -90,7 +90,7 @@ __device__ __forceinline__ void aph_store4(double* __restrict__ out, const doubl
 // scattered, u = x - x̄, phi_s = p_s sum_k (z - x)(W - y) (:185-195) and
 // out = {sum p (|u|^2 + |ȳ|^2 / gamma), sum phi, sum p |u|^2, sum p |ȳ|^2}
 __global__ void __launch_bounds__(GR_T)
-k_aph_norms(phgpu_state st, double gamma, const double* __restrict__ planes, const double* __restrict__ x,
+k_aph_norms(ph_tree st, double gamma, const double* __restrict__ planes, const double* __restrict__ x,
             const double* __restrict__ y, const double* __restrict__ W, const double* __restrict__ z,
             double* __restrict__ xbar, double* __restrict__ u, double* __restrict__ phi,
             double* __restrict__ bpart, int32_t* __restrict__ cnt, double* __restrict__ out) {
@@ -129,7 +129,7 @@ k_aph_norms(phgpu_state st, double gamma, const double* __restrict__ planes, con
 // ..}): theta, W += theta u, z = x̄ (first) or z + theta ȳ / gamma, the post-step phi (:756) and
 // out = {sum p W^2, sum p z^2, theta, sum phi}
 __global__ void __launch_bounds__(GR_T)
-k_aph_update(phgpu_state st, int first, double nu, double gamma, const double* __restrict__ red,
+k_aph_update(ph_tree st, int first, double nu, double gamma, const double* __restrict__ red,
              const double* __restrict__ planes, const double* __restrict__ x, const double* __restrict__ y,
              const double* __restrict__ u, double* __restrict__ W, double* __restrict__ z,
              double* __restrict__ phi, double* __restrict__ bpart, int32_t* __restrict__ cnt,
@@ -169,7 +169,7 @@ k_aph_update(phgpu_state st, int first, double nu, double gamma, const double* _
 // every scenario's next first key: round robin (:610-611) last_iter, else (:626-629)
 // -max(last_iter, shelf_life - 1), as the reference writes it.
 __global__ void __launch_bounds__(GR_T)
-k_aph_mark(phgpu_state st, const int32_t* __restrict__ mask, int iter, int shelf_life, int round_robin,
+k_aph_mark(ph_tree st, const int32_t* __restrict__ mask, int iter, int shelf_life, int round_robin,
            const double* __restrict__ phi, int32_t* __restrict__ last_iter, double* __restrict__ last_phi,
            double* __restrict__ k1, const double* __restrict__ W, const double* __restrict__ z,
            double* __restrict__ W_lag, double* __restrict__ z_lag) {

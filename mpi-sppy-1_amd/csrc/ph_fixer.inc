@@ -15,7 +15,7 @@
 
 // local scenarios of every node entry (nloc[num_nodes * nlen_max], cleared by the caller); the
 // grid and the wave vote of k_fixer_step: one atomic per wave where its scenarios share a node
-__global__ void __launch_bounds__(FX_T) k_fixer_nloc(phgpu_state st, int32_t* __restrict__ nloc) {
+__global__ void __launch_bounds__(FX_T) k_fixer_nloc(ph_tree st, int32_t* __restrict__ nloc) {
     const int64_t S = st.S;
     const int lane = threadIdx.x & (WAVE - 1);
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -63,7 +63,7 @@ __device__ __forceinline__ bool fixer_rule(bool iter0, double xb, double xsq, do
 
 template <bool SHARED>
 __global__ void __launch_bounds__(FX_T)
-k_fixer_step(phgpu_state st, phgpu_fixer_params prm, const double* __restrict__ node_buf,
+k_fixer_step(ph_data st, phgpu_fixer_params prm, const double* __restrict__ node_buf,
              const double* __restrict__ th, const int32_t* __restrict__ nb, const int32_t* __restrict__ lbl,
              const int32_t* __restrict__ ubl, int32_t* __restrict__ count, double* __restrict__ fixval,
              int32_t* __restrict__ acc, unsigned long long* __restrict__ totals) {

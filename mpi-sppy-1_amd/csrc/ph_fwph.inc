@@ -52,7 +52,7 @@ __device__ __forceinline__ double fw_G(const fwph_store& fw, int64_t S, int64_t 
 }
 
 // xq = sum a_j X_j, phi = sum a_j f_j over the K columns; xq also into the nonant columns of xqx
-__device__ __forceinline__ void fw_point(const phgpu_state& st, const fwph_store& fw, int64_t s, int K,
+__device__ __forceinline__ void fw_point(const ph_tree& st, const fwph_store& fw, int64_t s, int K,
                                          double* __restrict__ xq_out, double* __restrict__ xqx) {
     const int64_t S = st.S;
     const int nn = st.nn;
@@ -263,7 +263,7 @@ __device__ __forceinline__ void fw_lin(const fwph_store& fw, int nn, int64_t S, 
 
 // phgpu_fwph_load: the store of every scenario from K given columns, costs and weights
 __global__ void __launch_bounds__(FW_T)
-k_fw_load(phgpu_state st, fwph_store fw, int K, const double* __restrict__ X, const double* __restrict__ f,
+k_fw_load(ph_tree st, fwph_store fw, int K, const double* __restrict__ X, const double* __restrict__ f,
           const double* __restrict__ a, const double* __restrict__ rho, double* __restrict__ xq,
           double* __restrict__ xqx) {
     const int64_t S = st.S;
@@ -285,7 +285,7 @@ k_fw_load(phgpu_state st, fwph_store fw, int K, const double* __restrict__ X, co
 
 // phgpu_fwph_export: the store into the caller's arrays (each may be null)
 __global__ void __launch_bounds__(FW_T)
-k_fw_export(phgpu_state st, fwph_store fw, double* __restrict__ X, double* __restrict__ f, double* __restrict__ a,
+k_fw_export(ph_tree st, fwph_store fw, double* __restrict__ X, double* __restrict__ f, double* __restrict__ a,
             int32_t* __restrict__ ncols, double* __restrict__ xq, double* __restrict__ phi,
             int32_t* __restrict__ active, int32_t* __restrict__ nit) {
     const int64_t S = st.S;
@@ -311,7 +311,7 @@ k_fw_export(phgpu_state st, fwph_store fw, double* __restrict__ X, double* __res
 // fwph.py:227-247: What = W + rho (src - xbar), src = (1 - alpha) xbar + alpha xq at t = 0, else
 // xq; one nonant per grid row.  At t = 0 every scenario becomes active.
 __global__ void __launch_bounds__(GR_T)
-k_fw_direction(phgpu_state st, fwph_store fw, int t0, double alpha, const double* __restrict__ W,
+k_fw_direction(ph_tree st, fwph_store fw, int t0, double alpha, const double* __restrict__ W,
                const double* __restrict__ rho, const double* __restrict__ xbar, double* __restrict__ What) {
     const int64_t S = st.S;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -328,7 +328,7 @@ k_fw_direction(phgpu_state st, fwph_store fw, int t0, double alpha, const double
 // fwph.py:256-292 for every active scenario: Gamma, the new column, the QP, the break test; and
 // the three counts of the pass, stored last by the block with the last ticket.
 __global__ void __launch_bounds__(FW_T)
-k_fw_column(phgpu_state st, fwph_store fw, phgpu_fwph_params prm, int t0, const double* __restrict__ x,
+k_fw_column(ph_tree st, fwph_store fw, phgpu_fwph_params prm, int t0, const double* __restrict__ x,
             const double* __restrict__ obj, const double* __restrict__ bound, const int32_t* __restrict__ status,
             const double* __restrict__ W, const double* __restrict__ What, const double* __restrict__ rho,
             const double* __restrict__ xbar, double* __restrict__ gamma, double* __restrict__ dual_bound,
@@ -410,7 +410,7 @@ k_fw_column(phgpu_state st, fwph_store fw, phgpu_fwph_params prm, int t0, const 
 // thread adds its scenarios in index order, every block its threads in a fixed order, the block
 // with the last ticket the blocks' sums by a fixed tree (as k_w_diff): the same bits on every run.
 __global__ void __launch_bounds__(GR_T)
-k_fw_diff(phgpu_state st, fwph_store fw, const double* __restrict__ xbar, double* __restrict__ bpart,
+k_fw_diff(ph_tree st, fwph_store fw, const double* __restrict__ xbar, double* __restrict__ bpart,
           int32_t* __restrict__ cnt, double* __restrict__ out) {
     __shared__ double red[GR_T / WAVE];
     __shared__ double fin[WD_BLOCKS];

@@ -28,7 +28,7 @@ __device__ __forceinline__ int gm_segment(const int64_t* __restrict__ seg_ptr, i
 }
 
 __global__ void __launch_bounds__(BLOCK)
-k_gap_partial(phgpu_state st, const double* __restrict__ f_hat, const int32_t* __restrict__ st_hat,
+k_gap_partial(ph_tree st, const double* __restrict__ f_hat, const int32_t* __restrict__ st_hat,
               const double* __restrict__ f_star, const int32_t* __restrict__ st_star,
               const int64_t* __restrict__ seg_ptr, int nseg, int64_t s_off, double* __restrict__ part,
               int32_t* __restrict__ tag, double* __restrict__ out) {

@@ -646,7 +646,7 @@ k_ls_master(ls_store L, int64_t S, double eps, double eps_inf, int max_it, doubl
 //   planes 0 .. nn-1: p d_k,  nn: p (obj - d . x),  nn + 1: p obj,  nn + 2: 1 if not OPTIMAL
 // (a scenario that is not OPTIMAL contributes that count only).
 __global__ void __launch_bounds__(GR_T)
-k_ls_terms(phgpu_state st, ls_store L, const double* __restrict__ x, const double* __restrict__ y,
+k_ls_terms(ph_data st, ls_store L, const double* __restrict__ x, const double* __restrict__ y,
            const double* __restrict__ obj, const int32_t* __restrict__ status) {
     const int64_t S = st.S;
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

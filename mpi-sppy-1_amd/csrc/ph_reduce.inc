@@ -54,7 +54,7 @@ __global__ void __launch_bounds__(256) k_planes_clear(double* __restrict__ plane
 // MIXED = false: the caller's waves are uniform by construction (a two-stage-only entry
 // point): no test, no atomic route, planes unused.
 template <int MAXMASK, int NV, bool MIXED, typename Vals>
-__device__ __forceinline__ void node_partial(const phgpu_state& st, int64_t wave, int k, bool act, int gnode,
+__device__ __forceinline__ void node_partial(const ph_tree& st, int64_t wave, int k, bool act, int gnode,
                                              double* __restrict__ part, int32_t* __restrict__ tag,
                                              double* __restrict__ planes, Vals vals) {
     const bool lead = (threadIdx.x & (WAVE - 1)) == 0;
@@ -83,7 +83,7 @@ __device__ __forceinline__ void node_partial(const phgpu_state& st, int64_t wave
 
 // x̄ partial of nonant k over chunk w recomputed from x (a chunk of the path-6 epilogue
 // partials with a scenario the fallback solved; DESIGN.md 3.8), in scenario order
-__device__ __forceinline__ void xp_recompute(const phgpu_state& st, const double* __restrict__ x, int64_t w, int C,
+__device__ __forceinline__ void xp_recompute(const ph_tree& st, const double* __restrict__ x, int64_t w, int C,
                                              int k, double& a, double& b) {
     const int64_t S = st.S;
     const int d = st.nonant_depth[k], j = st.nonant_col[k];
@@ -108,7 +108,7 @@ __device__ __forceinline__ void xp_recompute(const phgpu_state& st, const double
 #define XF_THREADS 256
 template <int MAXMASK, int NV>
 __global__ void __launch_bounds__(XF_THREADS)
-k_node_final(phgpu_state st, const double* __restrict__ part, const int32_t* __restrict__ node,
+k_node_final(ph_tree st, const double* __restrict__ part, const int32_t* __restrict__ node,
              double* __restrict__ planes, int assign) {
     __shared__ int fnode[XF_THREADS], lnode[XF_THREADS];
     __shared__ double fv[NV][XF_THREADS], lv[NV][XF_THREADS];
@@ -236,7 +236,7 @@ k_node_final(phgpu_state st, const double* __restrict__ part, const int32_t* __r
 // kernel is on every PH iteration's critical path.
 // assign: node_buf was not cleared (one tree node, every entry is some nonant's): the fast
 // path stores its sums instead of adding them (phgpu_ph_reduce: one launch less per step)
-__global__ void __launch_bounds__(XF_THREADS) k_xbar_final(phgpu_state st, double* __restrict__ node_buf,
+__global__ void __launch_bounds__(XF_THREADS) k_xbar_final(ph_tree st, double* __restrict__ node_buf,
                                                            const int32_t* __restrict__ dirty = nullptr,
                                                            int xpC = 0, const double* __restrict__ x = nullptr,
                                                            int assign = 0) {
@@ -403,7 +403,7 @@ __device__ __forceinline__ void ticket_reset(int32_t* cnt) {
 // phbase.py:54-79: prob_coeff * x and prob_coeff * x^2 of each nonant, one nonant per grid
 // row (blockIdx.y; see k_ph_update), into st.part / st.part_node for k_xbar_final.
 __global__ void __launch_bounds__(BLOCK)
-k_xbar_partial(phgpu_state st, const double* __restrict__ x, double* __restrict__ node_buf, int clear) {
+k_xbar_partial(ph_tree st, const double* __restrict__ x, double* __restrict__ node_buf, int clear) {
     const int64_t S = st.S;
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool act = s < S;
@@ -429,7 +429,7 @@ k_xbar_partial(phgpu_state st, const double* __restrict__ x, double* __restrict_
 // out[0] |= 1 if some wave of local scenarios spans two nodes at a nonant's depth (the
 // test node_partial makes per wave)
 // out[1] |= 1 if some local scenario's node at a nonant's depth differs from scenario 0's
-__global__ void __launch_bounds__(BLOCK) k_xbar_mixed(phgpu_state st, int32_t* __restrict__ out) {
+__global__ void __launch_bounds__(BLOCK) k_xbar_mixed(ph_tree st, int32_t* __restrict__ out) {
     const int64_t S = st.S;
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool act = s < S;
@@ -447,7 +447,7 @@ __global__ void __launch_bounds__(BLOCK) k_xbar_mixed(phgpu_state st, int32_t* _
 
 // ------------------------------------------------------------------ adaptive rho
 // The residual sums of NormRhoUpdater and the two convergers (include/phgpu.h
-// phgpu_ph_residuals), four sums per (wave, nonant) in partials of their own (st.rs).
+// phgpu_ph_residuals), four sums per (wave, nonant) in partials of their own (ws: the handle's rs).
 #define RS_NV 4  // planes: prob |x - x̄|, pcoef |x - x̄|, rho, prob rho
 
 // norm_rho_updater.py:73-83 (plane 0), primal_dual_converger.py:66-82 and 96-107 (planes 1,
@@ -456,7 +456,7 @@ __global__ void __launch_bounds__(BLOCK) k_xbar_mixed(phgpu_state st, int32_t* _
 // scenarios are in tree order, so a node's scenarios are one run, and the lane at the end of a
 // run stores its rho.
 __global__ void __launch_bounds__(BLOCK)
-k_resid_partial(phgpu_state st, const double* __restrict__ x, const double* __restrict__ xbar,
+k_resid_partial(ph_tree st, ph_ws ws, const double* __restrict__ x, const double* __restrict__ xbar,
                 const double* __restrict__ rho, double* __restrict__ planes, double* __restrict__ rho_last) {
     const int64_t S = st.S;
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -473,7 +473,7 @@ k_resid_partial(phgpu_state st, const double* __restrict__ x, const double* __re
     // (the products formed here, ahead of node_partial, on purpose: not fused into the sums)
     const double v[RS_NV] = {pi * ad, pc * ad, r, pi * r};
     if (act && gnext != gnode) rho_last[gnode * st.nlen_max + st.nonant_off[k]] = r;
-    node_partial<0, RS_NV, true>(st, s / WAVE, k, act, gnode, st.rs.part, st.rs.tag, planes, [&](double(&o)[RS_NV]) {
+    node_partial<0, RS_NV, true>(st, s / WAVE, k, act, gnode, ws.part, ws.tag, planes, [&](double(&o)[RS_NV]) {
 #pragma unroll
         for (int j = 0; j < RS_NV; ++j) o[j] = v[j];
     });
@@ -487,7 +487,7 @@ k_resid_partial(phgpu_state st, const double* __restrict__ x, const double* __re
 #define NR_T 256
 #define NR_U 4
 __global__ void __launch_bounds__(NR_T)
-k_norm_rho_update(phgpu_state st, phgpu_norm_rho_params prm, const double* __restrict__ plane0,
+k_norm_rho_update(ph_tree st, phgpu_norm_rho_params prm, const double* __restrict__ plane0,
                   const double* __restrict__ rho_last, const double* __restrict__ xbar_node,
                   const double* __restrict__ xbar_prev, double* __restrict__ rho,
                   unsigned long long* __restrict__ counts) {
@@ -554,7 +554,7 @@ k_norm_rho_update(phgpu_state st, phgpu_norm_rho_params prm, const double* __res
 // both), for k_node_final<0xC, 4>.  One lane per scenario, NS_KU nonants per grid row.
 #define NS_KU 4  // nonants per grid row: their loads are in flight together
 __global__ void __launch_bounds__(BLOCK)
-k_nstats_partial(phgpu_state st, const double* __restrict__ v, double* __restrict__ planes) {
+k_nstats_partial(ph_tree st, ph_ws ws, const double* __restrict__ v, double* __restrict__ planes) {
     const int64_t S = st.S;
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool act = s < S;
@@ -577,7 +577,7 @@ k_nstats_partial(phgpu_state st, const double* __restrict__ v, double* __restric
         // (the products formed here, ahead of node_partial, on purpose: not fused into the sums)
         const double w[RS_NV] = {pc[u] * val[u], pc[u] * val[u] * val[u], act ? -val[u] : -INFINITY,
                                  act ? val[u] : -INFINITY};
-        node_partial<0xC, RS_NV, true>(st, s / WAVE, k, act, gn[u], st.ns.part, st.ns.tag, planes, [&](double(&o)[RS_NV]) {
+        node_partial<0xC, RS_NV, true>(st, s / WAVE, k, act, gn[u], ws.part, ws.tag, planes, [&](double(&o)[RS_NV]) {
 #pragma unroll
             for (int j = 0; j < RS_NV; ++j) o[j] = w[j];
         });
@@ -615,7 +615,7 @@ __device__ __forceinline__ void block_argmin(double& d, double& i, double* rd, d
 }
 
 __global__ void __launch_bounds__(NC_T)
-k_nonant_closest(phgpu_state st, const double* __restrict__ v, const double* __restrict__ xbar_node,
+k_nonant_closest(ph_tree st, const double* __restrict__ v, const double* __restrict__ xbar_node,
                  const double* __restrict__ xsqbar_node, double* __restrict__ dist, double* __restrict__ bpart,
                  int32_t* __restrict__ cnt, double* __restrict__ best) {
     __shared__ double rd[NC_T / WAVE], ri[NC_T / WAVE];
@@ -668,7 +668,7 @@ k_nonant_closest(phgpu_state st, const double* __restrict__ v, const double* __r
 // c and q of column j of scenario s in original units: the library's copies, or on a
 // shared-matrix handle words 0 and 1 of the column's per-scenario record (k_sh_fill; every
 // nonant column has one)
-__device__ __forceinline__ void obj_cq(const phgpu_state& st, int j, int64_t s, double& c, double& q) {
+__device__ __forceinline__ void obj_cq(const ph_data& st, int j, int64_t s, double& c, double& q) {
     if (st.shared) {
         const double* e = st.sk + (size_t)s * (size_t)st.sk_stride + st.sk_PC + 8 * (size_t)st.cmap[j];
         c = e[0];
@@ -682,7 +682,7 @@ __device__ __forceinline__ void obj_cq(const phgpu_state& st, int j, int64_t s, 
 // gradient.py:65-81 for f(x) = c.x + 1/2 x.diag(q).x: cost[k, s] = -(c + q xn[k, s]), one
 // nonant per grid row
 __global__ void __launch_bounds__(GR_T)
-k_grad_cost(phgpu_state st, const double* __restrict__ xn, double* __restrict__ cost) {
+k_grad_cost(ph_data st, const double* __restrict__ xn, double* __restrict__ cost) {
     const int64_t S = st.S;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int k = blockIdx.y; k < st.nn; k += gridDim.y) {  // (more nonants than grid rows: strided)
@@ -743,8 +743,8 @@ k_w_diff(const double* __restrict__ W, double* __restrict__ W_prev, int64_t tot,
 }
 
 // find_rho.py:170-203 up to the order statistic, for a two-stage handle: r[k, s] = |cost[k, s]|
-// / denominator and, per nonant, the per-wave partials (st.rr) of sum r, max(-r) and max(r)
-// for k_node_final<0x6, 3>.  One lane per scenario.
+// / denominator and, per nonant, the per-wave partials (ws: the handle's rr) of sum r, max(-r)
+// and max(r) for k_node_final<0x6, 3>.  One lane per scenario.
 //   gden == null: the scenario's own denominator, the largest over its nonants j of
 //     max(|x_j - x̄_j|, 2 (x_j - x̄_j)^2): np.max((w_denom, prox_denom)) at find_rho.py:189
 //     is ONE scalar per scenario (:78-115);
@@ -752,7 +752,7 @@ k_w_diff(const double* __restrict__ W, double* __restrict__ W_prev, int64_t tot,
 // IEEE division (numpy's): a zero denominator gives +inf (0 / 0 NaN, which fmax drops).
 #define RR_NV 3  // planes: sum r, max(-r), max(r)
 __global__ void __launch_bounds__(BLOCK)
-k_rho_ratio_partial(phgpu_state st, const double* __restrict__ cost, const double* __restrict__ x,
+k_rho_ratio_partial(ph_tree st, ph_ws ws, const double* __restrict__ cost, const double* __restrict__ x,
                     const double* __restrict__ xbar, const double* __restrict__ gden) {
     const int64_t S = st.S;
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -769,7 +769,7 @@ k_rho_ratio_partial(phgpu_state st, const double* __restrict__ cost, const doubl
     for (int k = 0; k < nn; ++k) {
         double r = 0.0;
         if (act) r = fabs(cost[IX(k)]) / (gden ? gden[st.nonant_off[k]] : d);
-        node_partial<0x6, RR_NV, false>(st, s / WAVE, k, act, gnode, st.rr.part, st.rr.tag, nullptr, [&](double(&v)[RR_NV]) {
+        node_partial<0x6, RR_NV, false>(st, s / WAVE, k, act, gnode, ws.part, ws.tag, nullptr, [&](double(&v)[RR_NV]) {
             v[0] = r;
             v[1] = act ? -r : -INFINITY;
             v[2] = act ? r : -INFINITY;
@@ -784,7 +784,7 @@ k_rho_ratio_partial(phgpu_state st, const double* __restrict__ cost, const doubl
 // gate itself (two cached loads); a closed gate stores nothing to rho.  One nonant per grid
 // row; applied (may be null) is stored by the grid's first thread.
 __global__ void __launch_bounds__(GR_T)
-k_rho_from_stats(phgpu_state st, const double* __restrict__ planes, double s_total, double alpha,
+k_rho_from_stats(ph_tree st, const double* __restrict__ planes, double s_total, double alpha,
                  const double* __restrict__ gate, double thr, double* __restrict__ rho,
                  int32_t* __restrict__ applied) {
     const int64_t S = st.S;
@@ -879,7 +879,7 @@ __device__ __forceinline__ void conv_last_block(double acc, const conv_sink& o) 
 #define UPD_BLOCKS 256  // at most about this many blocks: each takes a ticket on one counter
 #define UPD_U 4         // scenarios per thread in flight per trip
 __global__ void __launch_bounds__(UPD_T)
-k_ph_update(phgpu_state st, const double* __restrict__ x, const double* __restrict__ node_buf,
+k_ph_update(ph_tree st, const double* __restrict__ x, const double* __restrict__ node_buf,
             double* __restrict__ xbar, double* __restrict__ W, const double* __restrict__ rho,
             int update_W, conv_sink o) {
     // one nonant per grid row (blockIdx.y): the per-nonant index loads of a scenario's
@@ -935,7 +935,7 @@ k_ph_update(phgpu_state st, const double* __restrict__ x, const double* __restri
 // st.nwaves then point at those; dirty chunks are recomputed from x).  Few, large blocks for
 // a large batch (every block re-sums the partials), 256 threads for a small one.
 __global__ void __launch_bounds__(XL_T)
-k_ph_update_local(phgpu_state st, const double* __restrict__ x, double* __restrict__ node_buf,
+k_ph_update_local(ph_tree st, const double* __restrict__ x, double* __restrict__ node_buf,
                   double* __restrict__ xbar, double* __restrict__ W, const double* __restrict__ rho,
                   int update_W, conv_sink o, const int32_t* __restrict__ dirty, int C) {
     __shared__ double sa[XL_T / WAVE][XL_NN_MAX], sb[XL_T / WAVE][XL_NN_MAX];
@@ -1037,7 +1037,7 @@ k_ph_update_local(phgpu_state st, const double* __restrict__ x, double* __restri
 
 // spopt.py:310-439 local sums: prob*obj, prob*bound, prob, prob*feasible, prob*optimal.
 __global__ void __launch_bounds__(BLOCK)
-k_expect_partial(phgpu_state st, const double* __restrict__ obj, const double* __restrict__ bound,
+k_expect_partial(ph_tree st, const double* __restrict__ obj, const double* __restrict__ bound,
                  const int32_t* __restrict__ status) {
     const int64_t S = st.S;
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -453,7 +453,7 @@ static bool ipm_eligible(const phgpu_state* h) {
 #define IPMF_FIN_ALL 4
 #define IPMF_EQ 8
 
-__global__ void __launch_bounds__(256) k_ipm_flags(phgpu_state st, int32_t* __restrict__ flags,
+__global__ void __launch_bounds__(256) k_ipm_flags(ph_data st, int32_t* __restrict__ flags,
                                                    double* __restrict__ v0) {
     const int64_t S = st.S;
     const int n = st.n, m = st.m, nnz = st.nnz;
@@ -1245,7 +1245,7 @@ static int ipm_launch(phgpu_state* h, const solve_params& P, double* x, double* 
         HIPCHK(hipModuleLaunchKernel(im->fn_ipm, (unsigned)h->S, 1, 1, (unsigned)im->L, 1, 1, 0, st, args, nullptr));
         // the fallback: the global-memory PDHG (path 1) over the list, warm-started from the
         // IPM's hand-over (x_w / y_w / omega_w), adding its scenarios' statistics
-        phgpu_state v = *h;
+        pdhg_view v = *h;
         v.x = h->xw;
         v.y = h->yw;
         v.omega = h->omega_w;

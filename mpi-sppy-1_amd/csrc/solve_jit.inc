@@ -52,7 +52,7 @@ static bool jit_eligible(const phgpu_state* h) {
 
 // kinds[j] (columns): bit 0 a finite lb in some scenario, bit 1 a finite ub, bit 2 a
 // nonzero q; kinds[n + i] (rows): bit 0 a finite rl, bit 1 a finite ru, bit 2 rl != ru
-__global__ void __launch_bounds__(256) k_jit_kinds(phgpu_state st, int32_t* __restrict__ kinds) {
+__global__ void __launch_bounds__(256) k_jit_kinds(ph_data st, int32_t* __restrict__ kinds) {
     const int64_t S = st.S;
     const int e = blockIdx.x;
     int bits = 0;

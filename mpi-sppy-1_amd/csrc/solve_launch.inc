@@ -150,7 +150,7 @@ static int launch_stream(phgpu_state* h, const solve_params& P, double* x, doubl
         const char* bbe = getenv("PHGPU_SPLIT_BAR_BASE");
         unsigned gbase = bbe ? (unsigned)strtoul(bbe, nullptr, 0) : 0u;
         HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(h->split_part + (size_t)2 * G * 8), (int)gbase, (size_t)32 * ncl, st));
-        phgpu_state hv = *h;
+        pdhg_view hv = *h;  // k_solve_stream's first parameter: the argument array passes addresses
         solve_params Pv = P;
         int32_t* qh = h->qhead;
         double* gp = h->split_part;

@@ -147,7 +147,7 @@ struct reg_waves { static constexpr int value = ZR > 8 ? 1 : REG_WAVES_PER_EU; }
 
 template <int KC, int ZC, int KR, int ZR, bool REC>
 __global__ void __launch_bounds__(WAVE * REG_WPB) __attribute__((amdgpu_waves_per_eu(reg_waves<ZR>::value)))
-k_solve_reg(phgpu_state st, solve_params P, reg_plan pl, int* __restrict__ qhead, int64_t first_dyn,
+k_solve_reg(pdhg_view st, solve_params P, reg_plan pl, int* __restrict__ qhead, int64_t first_dyn,
             double* __restrict__ xout, double* __restrict__ yout, double* __restrict__ obj,
             double* __restrict__ bound, int32_t* __restrict__ status, int32_t* __restrict__ iters) {
     extern __shared__ double lds[];
@@ -753,7 +753,7 @@ __global__ void __launch_bounds__(ORDER_BINS) k_reg_order(const int32_t* __restr
 }
 
 // ------------------------------------------------------------------ instances
-typedef void (*reg_kernel_t)(phgpu_state, solve_params, reg_plan, int*, int64_t, double*, double*,
+typedef void (*reg_kernel_t)(pdhg_view, solve_params, reg_plan, int*, int64_t, double*, double*,
                              double*, double*, int32_t*, int32_t*);
 
 struct reg_instance {

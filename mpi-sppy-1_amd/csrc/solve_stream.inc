@@ -186,7 +186,7 @@ __device__ __forceinline__ void sell_dot_b(const int32_t* __restrict__ idx, cons
 // Partials: gpart [ncl][2][K][8], then the clusters' barrier counters 128 B apart.
 template <int B, bool SPLIT = false>
 __global__ void __launch_bounds__(SBLK, B == 1 ? 8 : 4)
-k_solve_stream(phgpu_state st, solve_params P, int* __restrict__ qhead, double* __restrict__ xout,
+k_solve_stream(pdhg_view st, solve_params P, int* __restrict__ qhead, double* __restrict__ xout,
                double* __restrict__ yout, double* __restrict__ obj, double* __restrict__ bound,
                int32_t* __restrict__ status, int32_t* __restrict__ iters, int q0, double* __restrict__ gpart,
                unsigned gbase, int ncl) {
@@ -690,14 +690,14 @@ __global__ void __launch_bounds__(256) k_sh_take0(const double* __restrict__ in,
     if (k < K) out[k] = in[(size_t)k * (size_t)S];
 }
 
-__global__ void __launch_bounds__(256) k_sh_init(phgpu_state st) {
+__global__ void __launch_bounds__(256) k_sh_init(ph_data st) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k < st.nnz) st.Ah_csr[k] = st.A[k];
     if (k < st.m) st.Dr[k] = 1.0;
     if (k < st.n) st.Dc[k] = 1.0;
 }
 
-__global__ void __launch_bounds__(256) k_sh_rowfac(phgpu_state st, int pc, double* __restrict__ rf) {
+__global__ void __launch_bounds__(256) k_sh_rowfac(ph_data st, int pc, double* __restrict__ rf) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= st.m) return;
     double a = 0.0;
@@ -708,7 +708,7 @@ __global__ void __launch_bounds__(256) k_sh_rowfac(phgpu_state st, int pc, doubl
     rf[i] = a > 0.0 ? 1.0 / sqrt(a) : 1.0;
 }
 
-__global__ void __launch_bounds__(256) k_sh_colfac(phgpu_state st, int pc, double* __restrict__ cf) {
+__global__ void __launch_bounds__(256) k_sh_colfac(ph_data st, int pc, double* __restrict__ cf) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= st.n) return;
     double a = 0.0;
@@ -719,7 +719,7 @@ __global__ void __launch_bounds__(256) k_sh_colfac(phgpu_state st, int pc, doubl
     cf[j] = a > 0.0 ? 1.0 / sqrt(a) : 1.0;
 }
 
-__global__ void __launch_bounds__(256) k_sh_apply(phgpu_state st, const double* __restrict__ rf,
+__global__ void __launch_bounds__(256) k_sh_apply(ph_data st, const double* __restrict__ rf,
                                                   const double* __restrict__ cf) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k < st.nnz) st.Ah_csr[k] *= rf[st.row_of[k]] * cf[st.col_idx[k]];
@@ -727,17 +727,17 @@ __global__ void __launch_bounds__(256) k_sh_apply(phgpu_state st, const double* 
     if (k < st.n) st.Dc[k] *= cf[k];
 }
 
-__global__ void __launch_bounds__(256) k_sh_csc(phgpu_state st) {
+__global__ void __launch_bounds__(256) k_sh_csc(ph_data st) {
     const int kc = blockIdx.x * blockDim.x + threadIdx.x;
     if (kc < st.nnz) st.Ah_csc[kc] = st.Ah_csr[st.perm[kc]];
 }
 
-__global__ void __launch_bounds__(256) k_sh_vinit(phgpu_state st, double* __restrict__ v) {
+__global__ void __launch_bounds__(256) k_sh_vinit(ph_data st, double* __restrict__ v) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j < st.n) v[j] = 1.0 + 0.5 * sin(1.7 * j);
 }
 
-__global__ void __launch_bounds__(256) k_sh_rowmv(phgpu_state st, const double* __restrict__ v,
+__global__ void __launch_bounds__(256) k_sh_rowmv(ph_data st, const double* __restrict__ v,
                                                   double* __restrict__ w) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= st.m) return;
@@ -747,7 +747,7 @@ __global__ void __launch_bounds__(256) k_sh_rowmv(phgpu_state st, const double* 
 }
 
 // u = A^T w and per-block partial sums of u^2
-__global__ void __launch_bounds__(256) k_sh_colmv(phgpu_state st, const double* __restrict__ w,
+__global__ void __launch_bounds__(256) k_sh_colmv(ph_data st, const double* __restrict__ w,
                                                   double* __restrict__ u, double* __restrict__ part) {
     __shared__ double sh[256];
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -779,21 +779,21 @@ __global__ void __launch_bounds__(256) k_sh_norm(const double* __restrict__ part
     if (threadIdx.x == 0) out[0] = sqrt(sh[0]);
 }
 
-__global__ void __launch_bounds__(256) k_sh_normalize(phgpu_state st, const double* __restrict__ u,
+__global__ void __launch_bounds__(256) k_sh_normalize(ph_data st, const double* __restrict__ u,
                                                       const double* __restrict__ nv, double* __restrict__ v) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     const double inv = nv[0] > 0.0 ? 1.0 / nv[0] : 0.0;
     if (j < st.n) v[j] = u[j] * inv;
 }
 
-__global__ void k_sh_finish_norm(phgpu_state st) {
+__global__ void k_sh_finish_norm(ph_data st) {
     // power iteration under-estimates ||A||_2: 1% margin (k_setup)
     const double lam = st.sh_norm[3];
     st.sh_norm[0] = lam > 0.0 ? 1.01 * sqrt(lam) : 1.0;
 }
 
 // shared base of the per-column / per-row data: scenario 0's values, scaled
-__global__ void __launch_bounds__(256) k_sh_base(phgpu_state st, const double* __restrict__ c,
+__global__ void __launch_bounds__(256) k_sh_base(ph_data st, const double* __restrict__ c,
                                                  const double* __restrict__ q, const double* __restrict__ lb,
                                                  const double* __restrict__ ub, const double* __restrict__ rl,
                                                  const double* __restrict__ ru) {
@@ -841,7 +841,7 @@ __global__ void __launch_bounds__(256) k_sh_vary(const double* __restrict__ a, c
 
 // per-scenario column / row data into the records: PC = {c, q, lb, ub, ch, qh, lbh, ubh}
 // (ch / qh are filled per solve), PR = {rlh, ruh, rl, ru}
-__global__ void __launch_bounds__(256) k_sh_fill(phgpu_state st, const double* __restrict__ c,
+__global__ void __launch_bounds__(256) k_sh_fill(ph_data st, const double* __restrict__ c,
                                                  const double* __restrict__ q, const double* __restrict__ lb,
                                                  const double* __restrict__ ub, const double* __restrict__ rl,
                                                  const double* __restrict__ ru) {
@@ -880,7 +880,7 @@ __global__ void __launch_bounds__(256) k_sh_fill(phgpu_state st, const double* _
 
 // norms of the shared part: sh_norm[1] = sum over shared columns of c^2, sh_norm[2] =
 // sum over shared rows of the finite row bounds squared (one block, fixed order)
-__global__ void __launch_bounds__(256) k_sh_normbase(phgpu_state st, const double* __restrict__ c,
+__global__ void __launch_bounds__(256) k_sh_normbase(ph_data st, const double* __restrict__ c,
                                                      const double* __restrict__ rl, const double* __restrict__ ru) {
     __shared__ double sh[2][256];
     const size_t S = (size_t)st.S;
@@ -912,13 +912,13 @@ __global__ void __launch_bounds__(256) k_sh_normbase(phgpu_state st, const doubl
     }
 }
 
-__global__ void __launch_bounds__(256) k_sh_fill_omega(phgpu_state st) {
+__global__ void __launch_bounds__(256) k_sh_fill_omega(pdhg_view st) {
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s < st.S) st.omega[s] = 1.0;
 }
 
 // phgpu_fix_nonants on a shared-matrix handle: the working bounds live in PC
-__global__ void __launch_bounds__(256) k_fix_nonants_sh(phgpu_state st, const double* __restrict__ xfix) {
+__global__ void __launch_bounds__(256) k_fix_nonants_sh(ph_data st, const double* __restrict__ xfix) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (int64_t)st.nn * st.S) return;
     const int64_t s = t / st.nn;
@@ -949,7 +949,7 @@ __global__ void __launch_bounds__(256) k_sh_sell_vals(const int32_t* __restrict_
 // solve's iterations (descending, ties by index) -- a permutation; O(S^2) compares, used
 // up to STREAM_ORDER_MAX scenarios
 #define STREAM_ORDER_MAX 16384
-__global__ void __launch_bounds__(256) k_stream_order(phgpu_state st) {
+__global__ void __launch_bounds__(256) k_stream_order(pdhg_view st) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= st.S) return;
     const int S = (int)st.S;
@@ -962,7 +962,7 @@ __global__ void __launch_bounds__(256) k_stream_order(phgpu_state st) {
     st.sk_order[r] = s;
 }
 
-__global__ void __launch_bounds__(256) k_stream_order_identity(phgpu_state st) {
+__global__ void __launch_bounds__(256) k_stream_order_identity(pdhg_view st) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s < st.S) st.sk_order[s] = s;
 }

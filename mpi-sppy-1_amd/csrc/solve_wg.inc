@@ -81,7 +81,7 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double* red, int& par
 
 template <int KC, int ZC, int KR, int ZR, int WPS>
 __global__ void __launch_bounds__(WAVE * WPS) __attribute__((amdgpu_waves_per_eu(WG_WAVES_PER_EU)))
-k_solve_wg(phgpu_state st, solve_params P, wg_plan pl, int* __restrict__ qhead,
+k_solve_wg(pdhg_view st, solve_params P, wg_plan pl, int* __restrict__ qhead,
            double* __restrict__ xout, double* __restrict__ yout, double* __restrict__ obj,
            double* __restrict__ bound, int32_t* __restrict__ status, int32_t* __restrict__ iters) {
     extern __shared__ double lds[];
@@ -584,7 +584,7 @@ k_solve_wg(phgpu_state st, solve_params P, wg_plan pl, int* __restrict__ qhead,
 }
 
 // ------------------------------------------------------------------ instances
-typedef void (*wg_kernel_t)(phgpu_state, solve_params, wg_plan, int*, double*, double*, double*, double*,
+typedef void (*wg_kernel_t)(pdhg_view, solve_params, wg_plan, int*, double*, double*, double*, double*,
                             int32_t*, int32_t*);
 
 struct wg_instance {

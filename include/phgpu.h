@@ -20,6 +20,8 @@
  *                                          mpisppy/fwph/fwph.py:210-370, 528-547 -> phgpu_fwph_*
  *   - the L-shaped method's cuts and master LP
  *                                          mpisppy/opt/lshaped.py:477-560, 600-630 -> phgpu_lshaped_*
+ *   - the extensive form's solve (ExtensiveForm.solve_extensive_form, SchurComplement.solve)
+ *                                          mpisppy/opt/ef.py:60-140, opt/sc.py:60-105 -> phgpu_ef_*
  *   - the per-batch moments of the MMW gap estimators and of zhat4xhat
  *                                          mpisppy/confidence_intervals/ciutils.py:400-415 -> phgpu_gap_moments
  *   - APH's projective step, dispatch and partial solve loop (Update_y, Compute_Averages,
@@ -781,6 +783,65 @@ int phgpu_lshaped_load(phgpu_handle h, int32_t K, const int32_t* group, const do
                        const double* b, void* stream);
 int phgpu_lshaped_export(phgpu_handle h, int32_t* ncuts, int32_t* group, double* a, double* b,
                          void* stream);
+
+/* The extensive form (mpisppy/opt/ef.py ExtensiveForm.solve_extensive_form, mpisppy/opt/sc.py
+ * SchurComplement.solve), two-stage continuous problems, minimisation: ONE primal-dual interior
+ * point (Mehrotra's predictor-corrector) on the whole extensive form, decomposed by a Schur
+ * complement in the ROOT nonants z.  The reference builds one Pyomo model of all
+ * scenarios and hands it to a solver (ef.py:60-140), or gives the scenarios' blocks to parapint's
+ * Schur-complement linear solver over MPI (sc.py:60-105).  Here a lane per scenario factors
+ * N_s = W D W' + E (dense LDL', kept in the store scenario-fastest), the lanes' T' N_s^-1 T and
+ * T' N_s^-1 g are summed in a fixed order, one workgroup factors the nn x nn complement C and
+ * solves for dz, and a second pass per scenario back-substitutes.  Step lengths, mu and sigma are
+ * global.  An iteration is, per right-hand side (stage 0 the predictor, 1 the corrector),
+ *
+ *   phgpu_ef_schur -> [ranks: sum rsum, max rmax] -> phgpu_ef_direction -> [sum rsum[0:3], max
+ *   rmax[0:2]] -> phgpu_ef_step
+ *
+ * and every rank then holds the same bits of z, of the step lengths and of the test's numbers.
+ * All entries are ordered on the stream, none synchronises, the same input gives the same bits;
+ * -3 on a PHGPU_SHARED_MATRIX handle and on a tree with more than two stages.
+ *
+ * phgpu_ef_init: allocate the store (the handle's, counted in phgpu_workspace_bytes, freed by
+ * phgpu_destroy or by another init) and set the starting iterate.  HOST arrays [nn]: zlb < zub
+ * the nonants' tightest bounds over the scenarios of all ranks (infinite sides allowed; a fixed
+ * nonant is refused with -1), cz = sum_s p_s c_s[N], qz = sum_s p_s q_s[N] >= 0.  ncomp: the finite
+ * bounds of the whole extensive form (other columns, sides of the rows with rl < ru, z) over all
+ * ranks; cmax: max |c| over all ranks; tol: the relative KKT tolerance; qp: 1 takes a common
+ * primal and dual step.  Limits: nn <= 64, m <= 64 (any n and nnz); beyond them -1 with a message. */
+int phgpu_ef_init(phgpu_handle h, const double* zlb, const double* zub, const double* cz, const double* qz,
+                  double ncomp, double cmax, double tol, int32_t qp, void* stream);
+
+/* The scenario pass of one right-hand side and its sums over the local scenarios (device buffers).
+ *   stage 0: residuals, N_s and its factor, and
+ *     rsum [nn (nn + 1) / 2 + 2 nn + 2] = {sum_s T' N_s^-1 T (lower triangle by rows) | sum_s T' N_s^-1
+ *     g_s | sum_s T' y_s | sum of the products slack x dual | sum_s p_s f_s},
+ *     rmax [2] = {largest row residual over 1 + its sides, largest dual residual over p_s}
+ *   stage 1: the corrector's g on the same factors, rsum [nn] = sum_s T' N_s^-1 g_s.
+ * Several ranks sum rsum and take the maximum of rmax (stage 0) before phgpu_ef_direction. */
+int phgpu_ef_schur(phgpu_handle h, int32_t stage, double* rsum, double* rmax, void* stream);
+
+/* One workgroup: at stage 0 the test of the iterate, then C = Dz^-1 + rsum's triangle and its
+ * Cholesky factor in LDS (kept for stage 1); the solve C dz = -r_z + rsum's right-hand side.  Then
+ * the direction pass (dy_s = N_s^-1 (g_s - T dz), dx, dw, the bound duals) and its reductions:
+ * rsum [3] = sums of {s dz, ds z, ds dz} (the affine mu is a polynomial in the step lengths),
+ * rmax [2] = the largest -ds / s and -dz / z.  Several ranks sum and take the maximum again.
+ *   info: double[8], device or host-mapped pinned memory, stored at stage 0 only: {iteration, mu,
+ *   primal, dual, gap residual, objective sum_s p_s f_s, done (1: the iterate passes tol; every
+ *   later call then leaves the iterate alone), iteration again (stored last)}. */
+int phgpu_ef_direction(phgpu_handle h, int32_t stage, double* rsum, double* rmax, double* info, void* stream);
+
+/* stage 0: the affine step lengths, sigma = (mu_aff / mu)^3 (at least 1/2 once mu has not halved in
+ * five iterations), the affine direction kept for the second-order term.  stage 1: the step
+ * lengths (0.995 of the way to the boundary; the minimum over all scenarios and z), the step. */
+int phgpu_ef_step(phgpu_handle h, int32_t stage, const double* rsum, const double* rmax, void* stream);
+
+/* The iterate as a solve's outputs (phgpu_solve's buffers): z in every scenario's nonant columns
+ * (bitwise equal over the scenarios), y [m*S] the scenario's own row duals (the extensive form's
+ * over p_s; may be NULL), obj = bound = the scenario's own objective, status PHGPU_OPTIMAL once the
+ * test passed, else PHGPU_ITER_LIMIT, iters the interior-point iterations.  z [nn] device, may be NULL. */
+int phgpu_ef_export(phgpu_handle h, double* x, double* y, double* obj, double* bound, int32_t* status,
+                    int32_t* iters, double* z, void* stream);
 
 /* Free the workspace and the handle. */
 int phgpu_destroy(phgpu_handle h);

@@ -19,6 +19,7 @@ struct ipm_module;  // solve_ipm.inc: the hipRTC-compiled path-6 module of a han
 struct fwph_store;  // ph_fwph.inc: the FWPH column store of a handle
 struct sel_state;   // ph_aph.inc: the workspace of phgpu_select_smallest
 struct ls_store;    // ph_lshaped.inc: the cut store and master of the L-shaped method
+struct ef_store;    // ph_ef.inc: the iterate and work space of the extensive-form interior point
 struct ph_ws {      // a reduction's device workspace: partials, and node tags or a ticket counter
     double* part;
     int32_t* tag;
@@ -244,6 +245,9 @@ struct phgpu_state : pdhg_view {
     // phgpu_lshaped_*: the cut store, the master's data and work space (host record of its
     // device buffers; null until phgpu_lshaped_init)
     ls_store* ls;
+    // phgpu_ef_*: the extensive-form interior point's iterate, factors and work space (host record
+    // of its device buffers; null until phgpu_ef_init)
+    ef_store* ef;
     // phgpu_gap_moments: two slots of GM_NV partials per wave (its head and its tail run) and
     // their segment tags [2 * nwaves], allocated at its first call
     ph_ws gm;

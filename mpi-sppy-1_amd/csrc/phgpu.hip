@@ -25,6 +25,7 @@
 //                                       opt/aph.py:151-195, 254-310, 394-408, 453-496, 602-668
 //   the L-shaped method's cuts and master LP
 //                                       opt/lshaped.py:477-560, 600-666
+//   the extensive form's interior point  opt/ef.py:60-140, opt/sc.py:60-105 (ph_ef.inc)
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -843,6 +844,7 @@ __global__ void k_stats_copy(const unsigned long long* __restrict__ src, int cop
 #include "ph_fwph.inc"
 #include "ph_aph.inc"
 #include "ph_lshaped.inc"
+#include "ph_ef.inc"
 #include "ph_gap.inc"
 
 // Xhat_Eval._fix_nonants (utils/xhat_eval.py; spopt.py _fix_nonants): nonant columns of
@@ -3181,6 +3183,149 @@ extern "C" int phgpu_lshaped_export(phgpu_handle h, int32_t* ncuts, int32_t* gro
     return 0;
 }
 
+// ------------------------------------------------------------------ the extensive form (ph_ef.inc)
+static void ef_release(phgpu_state* h) {
+    ef_store* E = h->ef;
+    if (!E) return;
+    dfree(h, &E->x); dfree(h, &E->zl); dfree(h, &E->zu); dfree(h, &E->dx); dfree(h, &E->dxa); dfree(h, &E->D);
+    dfree(h, &E->w); dfree(h, &E->vl); dfree(h, &E->vu); dfree(h, &E->y); dfree(h, &E->dw); dfree(h, &E->dwa);
+    dfree(h, &E->dy); dfree(h, &E->dya); dfree(h, &E->g); dfree(h, &E->wk); dfree(h, &E->rp); dfree(h, &E->E);
+    dfree(h, &E->fac); dfree(h, &E->terms); dfree(h, &E->zd); dfree(h, &E->C); dfree(h, &E->ctl);
+    delete E;
+    h->ef = nullptr;
+}
+
+static inline int ef_nsum0(const ef_store& E) { return E.ntri + 2 * E.nn + 2; }
+
+// ef.py:60-100 / sc.py:60-100 (build the problem): the iterate's start
+extern "C" int phgpu_ef_init(phgpu_handle h, const double* zlb, const double* zub, const double* cz, const double* qz,
+                             double ncomp, double cmax, double tol, int32_t qp, void* stream) {
+    if (!h) return set_err(-1, "null handle");
+    if (!h->scen_set) return set_err(-1, "phgpu_ef_init: no scenario data yet");
+    if (h->shared) return set_err(-3, "phgpu_ef_init: a shared-matrix handle is not served");
+    if (h->depth != 1 || h->num_nodes != 1)
+        return set_err(-3, "phgpu_ef_init: two-stage handles only (depth %d, %d nodes)", h->depth, h->num_nodes);
+    if (h->nn < 1 || h->nn > EF_NN_MAX || h->m < 1 || h->m > EF_M_MAX)
+        return set_err(-1, "phgpu_ef_init: nn %d (1..%d), m %d (1..%d)", h->nn, EF_NN_MAX, h->m, EF_M_MAX);
+    if (!zlb || !zub || !cz || !qz) return set_err(-1, "null argument");
+    if (!(ncomp >= 1.0) || !(cmax >= 0.0) || !(tol > 0.0))
+        return set_err(-1, "phgpu_ef_init: ncomp %g, cmax %g, tol %g", ncomp, cmax, tol);
+    const int nn = h->nn, m = h->m, n = h->n;
+    for (int k = 0; k < nn; ++k)
+        if (!(zlb[k] < zub[k]) || zlb[k] == INFINITY || zub[k] == -INFINITY || !(qz[k] >= 0.0))
+            return set_err(-1, "phgpu_ef_init: nonant %d has bounds [%g, %g] (no interior) or q %g", k, zlb[k], zub[k],
+                           qz[k]);
+    FLUSH_STEP(h);
+    hipStream_t st = (hipStream_t)stream;
+    if (h->ef) {
+        HIPCHK(hipStreamSynchronize(st));  // (nothing of the old store may be in flight)
+        ef_release(h);
+    }
+    ef_store* E = new (std::nothrow) ef_store();
+    if (!E) return set_err(-3, "out of host memory");
+    memset(E, 0, sizeof(*E));
+    h->ef = E;
+    E->nn = nn; E->m = m; E->n = n; E->ntri = nn * (nn + 1) / 2; E->ld = nn | 1;
+    E->nplanes = ef_nsum0(*E) + 2;
+    const size_t S = (size_t)h->S;
+    int rc = 0;
+    for (double** p : {&E->x, &E->zl, &E->zu, &E->dx, &E->dxa, &E->D})
+        if (!rc) rc = dalloc(h, p, (size_t)n * S);
+    for (double** p : {&E->w, &E->vl, &E->vu, &E->y, &E->dw, &E->dwa, &E->dy, &E->dya, &E->g, &E->wk, &E->rp, &E->E})
+        if (!rc) rc = dalloc(h, p, (size_t)m * S);
+    if (!rc) rc = dalloc(h, &E->fac, (size_t)(m * (m + 1) / 2) * S);
+    if (!rc) rc = dalloc(h, &E->terms, (size_t)E->nplanes * S);
+    if (!rc) rc = dalloc(h, &E->C, (size_t)nn * E->ld);
+    if (!rc) rc = dalloc(h, &E->ctl, (size_t)EF_CTL);
+    std::vector<double> zd((size_t)(EZ_N + 1) * nn, 0.0), ctl(EF_CTL, 0.0);
+    for (int k = 0; k < nn; ++k) {
+        zd[(size_t)EZ_LB * nn + k] = zlb[k];
+        zd[(size_t)EZ_UB * nn + k] = zub[k];
+        zd[(size_t)EZ_C * nn + k] = cz[k];
+        zd[(size_t)EZ_Q * nn + k] = qz[k];
+        zd[(size_t)EZ_Z * nn + k] = ef_inside(zlb[k], zub[k]);
+        zd[(size_t)EZ_ZL * nn + k] = isfinite(zlb[k]) ? 1.0 + fabs(cz[k]) : 0.0;
+        zd[(size_t)EZ_ZU * nn + k] = isfinite(zub[k]) ? 1.0 + fabs(cz[k]) : 0.0;
+    }
+    ctl[EC_NCOMP] = ncomp; ctl[EC_CMAX] = cmax; ctl[EC_TOL] = tol; ctl[EC_QP] = qp ? 1.0 : 0.0;
+    if (!rc) rc = ls_upload(h, &E->zd, zd.data(), zd.size());
+    if (rc) {
+        ef_release(h);
+        return rc;
+    }
+    HIPCHK(hipMemcpy(E->ctl, ctl.data(), ctl.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(E->terms, 0, (size_t)E->nplanes * S * sizeof(double), st));
+    hipLaunchKernelGGL(k_ef_start, dim3((unsigned)((h->S + EF_T - 1) / EF_T)), dim3(EF_T), 0, st, *h, *E);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+#define EF_READY(h, who, stage)                                                              \
+    do {                                                                                     \
+        if (!(h)) return set_err(-1, "null handle");                                         \
+        if (!(h)->ef) return set_err(-1, who ": phgpu_ef_init has not run");                 \
+        if ((stage) != 0 && (stage) != 1) return set_err(-1, who ": stage %d", (int)(stage)); \
+        FLUSH_STEP(h);                                                                       \
+    } while (0)
+
+// the scenario pass and its sums over the local scenarios
+extern "C" int phgpu_ef_schur(phgpu_handle h, int32_t stage, double* rsum, double* rmax, void* stream) {
+    EF_READY(h, "phgpu_ef_schur", stage);
+    if (!rsum || !rmax) return set_err(-1, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    const ef_store& E = *h->ef;
+    const dim3 grid((unsigned)((h->S + EF_T - 1) / EF_T));
+    hipLaunchKernelGGL(k_ef_schur, grid, dim3(EF_T), 0, st, *h, E, (int)stage);
+    const int nsum = stage == 0 ? ef_nsum0(E) : E.nn, nmax = stage == 0 ? 2 : 0;
+    hipLaunchKernelGGL(k_ef_reduce, dim3((unsigned)(nsum + nmax)), dim3(GR_T), 0, st, E, h->S, nsum, rsum, rmax);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// the Schur complement's solve, the direction pass and its sums and maxima
+extern "C" int phgpu_ef_direction(phgpu_handle h, int32_t stage, double* rsum, double* rmax, double* info, void* stream) {
+    EF_READY(h, "phgpu_ef_direction", stage);
+    if (!rsum || !rmax || !info) return set_err(-1, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    const ef_store& E = *h->ef;
+    const size_t lds = ((size_t)E.nn * E.ld + E.nn) * sizeof(double);
+    hipLaunchKernelGGL(k_ef_solve, dim3(1), dim3(LS_T), lds, st, E, (int)stage, (const double*)rsum, (const double*)rmax,
+                       info);
+    const dim3 grid((unsigned)((h->S + EF_T - 1) / EF_T));
+    hipLaunchKernelGGL(k_ef_direction, grid, dim3(EF_T), 0, st, *h, E, (int)stage);
+    hipLaunchKernelGGL(k_ef_reduce, dim3(5), dim3(GR_T), 0, st, E, h->S, 3, rsum, rmax);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// the step lengths and sigma (stage 0), the step (stage 1)
+extern "C" int phgpu_ef_step(phgpu_handle h, int32_t stage, const double* rsum, const double* rmax, void* stream) {
+    EF_READY(h, "phgpu_ef_step", stage);
+    if (!rsum || !rmax) return set_err(-1, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    const ef_store& E = *h->ef;
+    const dim3 grid((unsigned)((h->S + EF_T - 1) / EF_T));
+    hipLaunchKernelGGL(k_ef_ctrl, dim3(1), dim3(WAVE), 0, st, E, (int)stage, rsum, rmax);
+    if (stage == 0) hipLaunchKernelGGL(k_ef_keep, grid, dim3(EF_T), 0, st, *h, E);
+    else hipLaunchKernelGGL(k_ef_step, grid, dim3(EF_T), 0, st, *h, E);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int phgpu_ef_export(phgpu_handle h, double* x, double* y, double* obj, double* bound, int32_t* status,
+                               int32_t* iters, double* z, void* stream) {
+    EF_READY(h, "phgpu_ef_export", 0);
+    if (!x || !obj || !bound || !status || !iters) return set_err(-1, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    const ef_store& E = *h->ef;
+    hipLaunchKernelGGL(k_ef_export, dim3((unsigned)((h->S + EF_T - 1) / EF_T)), dim3(EF_T), 0, st, *h, E, x, y, obj, bound,
+                       status, iters);
+    HIPCHK(hipGetLastError());
+    if (z) HIPCHK(hipMemcpyAsync(z, EF_Z(E, EZ_Z), (size_t)E.nn * sizeof(double), hipMemcpyDeviceToDevice, st));
+    h->last_stats = nullptr;
+    return 0;
+}
+
 #include "comm_rccl.inc"
 
 extern "C" int phgpu_destroy(phgpu_handle h) {
@@ -3191,6 +3336,7 @@ extern "C" int phgpu_destroy(phgpu_handle h) {
     module_release(h->ipm_loop);
     delete h->fw;  // (its device buffers are in allocs)
     delete h->ls;
+    delete h->ef;
     phgpu_owner* o = owner_of(h);  // (a deferred step that never ran is dropped with it)
     for (const dev_alloc& a : o->allocs) (void)hipFree(a.p);
     delete o;

@@ -12,7 +12,7 @@ function with one batch.
 
 DEPARTURES from the reference.  x* comes from ``LShapedMethod`` on the batch's scenarios (the
 reference solves the extensive form through the amalgamator); ``xstar_solver`` takes a caller's
-own.  The merged engine holds the probabilities the scenario creator gives each batch (1 / n), so
+own, and ``ef_xstar_solver`` makes one that does solve the extensive form (opt/ef.py).  The merged engine holds the probabilities the scenario creator gives each batch (1 / n), so
 they sum to the number of batches: every moment is divided by its segment's sum of probabilities,
 and no result depends on their common scale.  A scenario that is not solved to optimality in
 either solve raises (an estimator over a subset of its sample is not the estimator); the
@@ -291,6 +291,35 @@ def lshaped_xstar(m, scenario_names, scenario_creator_kwargs, solver_name, tol=1
     finally:
         if ls.engine is not None:
             ls.engine.close()
+
+
+def ef_xstar_solver(mname, solver_name=None, tol=1e-8, max_iter=100, device=None):
+    """A ready-made ``xstar_solver`` for ``gap_estimators`` / ``gap_estimators_batched``: the optimum
+    of each sample problem from ``ExtensiveForm`` (opt/ef.py: one interior point on the sample's
+    extensive form, LPs and diagonal QPs, no cut groups and no master rounds) instead of the L-shaped method,
+    which stays the default.  ``mname``: the model module or its name.  Returns the callable
+    (scenario_names, scenario_creator_kwargs) -> x* [nn]; a solve that does not reach ``tol``
+    within ``max_iter`` iterations raises."""
+    from ..opt.ef import ExtensiveForm
+    from ..spopt import SOLVER_NAMES
+    m = model_module(mname) if isinstance(mname, str) else mname
+
+    def solve(scenario_names, scenario_creator_kwargs):
+        opts = {"solver": solver_name or SOLVER_NAMES[0], "tol": tol, "max_iter": max_iter, "toc": False,
+                "device": device}
+        if hasattr(m, "batch_creator"):
+            opts["batch_creator"] = m.batch_creator
+        ef = ExtensiveForm(opts, scenario_names, m.scenario_creator, scenario_creator_kwargs=scenario_creator_kwargs)
+        try:
+            res = ef.solve_extensive_form()
+            if res.solver.termination_condition != "optimal":
+                raise RuntimeError(f"the extensive form over {scenario_names[0]}..{scenario_names[-1]} was not solved "
+                                   f"to tol {tol} in {max_iter} iterations")
+            return np.array(ef.root_nonants(), dtype=np.float64)
+        finally:
+            if ef.engine is not None:
+                ef.engine.close()
+    return solve
 
 
 # ------------------------------------------------------------------ the estimators

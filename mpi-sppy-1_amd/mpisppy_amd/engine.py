@@ -1497,6 +1497,86 @@ class PHEngine:
         K = int(K[0])
         return group[:K], a[:K], b[:K]
 
+    # -------------------------------------------------------------- extensive form
+    def ef_init(self, zlb, zub, cz, qz, ncomp, cmax, tol, qp):
+        """The interior point's store and starting iterate (phgpu_ef_init): host
+        arrays zlb, zub, cz, qz [nn] and the counts agreed over the ranks.  Buffers: ``ef_sum``
+        (the sums a pass gives to the ranks), ``ef_max`` [2], ``ef_z`` [nn] and the pinned
+        ``ef_info`` (phgpu_ef_direction's 8 doubles)."""
+        self._flush_step()
+        nn = self.nn
+        f8 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(nn))  # noqa: E731
+        zlb, zub, cz, qz = f8(zlb), f8(zub), f8(cz), f8(qz)
+        hp = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+        _lib.check(self.lib.phgpu_ef_init(self.h, hp(zlb), hp(zub), hp(cz), hp(qz), float(ncomp), float(cmax), float(tol),
+                                          int(bool(qp)), self._stream()), "phgpu_ef_init")
+        z = lambda *s: torch.zeros(*s, dtype=torch.float64, device=self.device)  # noqa: E731
+        self.ef_ntri = nn * (nn + 1) // 2
+        self.ef_sum = z(self.ef_ntri + 2 * nn + 2)
+        self.ef_max = z(2)
+        self.ef_z = z(nn)
+        self.ef_info = torch.zeros(8, dtype=torch.float64).pin_memory()
+        self._ef_info_np = self.ef_info.numpy()
+        self._ef_ev = torch.cuda.Event()
+        for k in ("ef_schur", "ef_direction", "ef_step", "allreduce_ef"):
+            self.calls[k] = 0
+
+    def _ef_ranks(self, nsum, nmax):
+        """The ranks' sum of ef_sum[:nsum] and maximum of ef_max[:nmax]."""
+        if self.comm.size > 1:
+            self.calls["allreduce_ef"] += 1 + (nmax > 0)
+            self._ar(self.ef_sum[:nsum] if nsum < self.ef_sum.numel() else self.ef_sum)
+            if nmax:
+                self.comm.allreduce_max_(self.ef_max)
+
+    def ef_schur(self, stage):
+        """The scenario pass of one right-hand side, summed over the local scenarios and the
+        ranks (phgpu_ef_schur).  Device work only."""
+        self.calls["ef_schur"] += 1
+        _lib.check(self.lib.phgpu_ef_schur(self.h, int(stage), _ptr(self.ef_sum), _ptr(self.ef_max), self._stream()),
+                   "phgpu_ef_schur")
+        self._ef_ranks(self.ef_sum.numel() if stage == 0 else self.nn, 2 if stage == 0 else 0)
+
+    def ef_direction(self, stage):
+        """The Schur complement's solve, the direction pass and its reductions over the ranks
+        (phgpu_ef_direction); stage 0 stores the iterate's test in ``ef_info``."""
+        self.calls["ef_direction"] += 1
+        if stage == 0:
+            self._ef_info_np[:] = np.nan
+        _lib.check(self.lib.phgpu_ef_direction(self.h, int(stage), _ptr(self.ef_sum), _ptr(self.ef_max),
+                                               ctypes.c_void_p(self.ef_info.data_ptr()), self._stream()),
+                   "phgpu_ef_direction")
+        if stage == 0:
+            self._ef_ev.record()
+        self._ef_ranks(3, 2)
+
+    def ef_step(self, stage):
+        """Sigma (stage 0) or the step (stage 1) (phgpu_ef_step).  Device work only."""
+        self.calls["ef_step"] += 1
+        _lib.check(self.lib.phgpu_ef_step(self.h, int(stage), _ptr(self.ef_sum), _ptr(self.ef_max), self._stream()),
+                   "phgpu_ef_step")
+
+    def ef_iteration(self):
+        """One predictor-corrector iteration: nothing is read on the host."""
+        for stage in (0, 1):
+            self.ef_schur(stage)
+            self.ef_direction(stage)
+            self.ef_step(stage)
+
+    def ef_read(self):
+        """The iteration's one read: a wait for the last stage-0 direction call and the pinned
+        ``ef_info`` as a dict (the test of the iterate that iteration started from)."""
+        self._ef_ev.synchronize()
+        v = self._ef_info_np
+        return {"iter": v[0], "mu": v[1], "pres": v[2], "dres": v[3], "gap": v[4], "obj": v[5], "done": v[6]}
+
+    def ef_export(self):
+        """The iterate into ``x``, ``y``, ``obj``, ``bound``, ``status``, ``iters`` and ``ef_z``
+        (phgpu_ef_export)."""
+        _lib.check(self.lib.phgpu_ef_export(self.h, _ptr(self.x), _ptr(self.y), _ptr(self.obj), _ptr(self.bound),
+                                            _ptr(self.status), _ptr(self.iters), _ptr(self.ef_z), self._stream()),
+                   "phgpu_ef_export")
+
     def fix_nonants_by_node(self, table):
         """Fix every local scenario's nonants at per-node values: ``table`` is a device
         [num_nodes, nlen_max] tensor (global node order of ``node_names``); nonant k of

@@ -101,6 +101,57 @@ class SPBase:
         if missing:
             raise ValueError(f"Missing option(s) {missing}")
 
+    # spbase.py:547-581
+    def gather_var_values_to_rank0(self, get_zero_prob_values=False):
+        """{(scenario name, nonant variable name): value} of all ranks' scenarios on rank 0, None on
+        the other ranks; None for a value whose variable probability is zero unless
+        ``get_zero_prob_values``.  The values are the models' (``load_solutions_to_models``), or
+        with a batch_creator the engine's last x."""
+        vals = {}
+        mask = getattr(self, "prob0_mask", None)
+        if self.local_scenarios:
+            for s, nm in enumerate(self.local_scenario_names):
+                k = 0
+                for nd in self.local_scenarios[nm]._mpisppy_node_list:
+                    for v in nd.nonant_vardata_list:
+                        zero = mask is not None and mask[s, k] == 0.0
+                        vals[nm, v.name] = None if zero and not get_zero_prob_values else v.value
+                        k += 1
+        else:
+            b = self.batch
+            x = self.engine.nonant_x()
+            names = b.nonant_names if b.nonant_names is not None else [f"x[{j}]" for j in b.nonant_col]
+            for s, nm in enumerate(self.local_scenario_names):
+                for k, vn in enumerate(names):
+                    zero = mask is not None and mask[s, k] == 0.0
+                    vals[nm, vn] = None if zero and not get_zero_prob_values else float(x[s, k])
+        if self.n_proc == 1:
+            return vals
+        every = self.mpicomm.gather_object(vals, root=0)
+        if self.cylinder_rank != 0:
+            return None
+        return {key: v for d in every for key, v in d.items()}
+
+    # spbase.py:584-616
+    def report_var_values_at_rank0(self, header="", print_zero_prob_values=False):
+        """Print the nonants of every scenario as a table, variables by scenarios, on rank 0."""
+        vals = self.gather_var_values_to_rank0(get_zero_prob_values=print_zero_prob_values)
+        if self.cylinder_rank != 0:
+            return
+        if header:
+            print(header)
+        snames = sorted({s for s, _ in vals})
+        vnames = sorted({v for _, v in vals})
+        vw = max(len(v) for v in vnames)
+        fw = max(10, max(len(s) for s in snames))
+        print(f"{'':<{vw}s} | " + "".join(f"{s:^{fw}s} " for s in snames))
+        for v in vnames:
+            cells = []
+            for s in snames:
+                val = vals[s, v]
+                cells.append(f"{'-':^{fw}s}" if val is None and not print_zero_prob_values else f"{val:{fw}.4f}")
+            print(f"{v:<{vw}} | " + " ".join(cells) + " ")
+
     # spbase.py:394-437
     def _use_variable_probability_setter(self, verbose=False):
         """Per-nonant probability coefficients (``variable_probability(model, **kwargs)`` ->

@@ -22,6 +22,8 @@
  *                                          mpisppy/opt/lshaped.py:477-560, 600-630 -> phgpu_lshaped_*
  *   - the extensive form's solve (ExtensiveForm.solve_extensive_form, SchurComplement.solve)
  *                                          mpisppy/opt/ef.py:60-140, opt/sc.py:60-105 -> phgpu_ef_*
+ *   - bundles: the extensive form of each bundle's scenarios as a PH subproblem
+ *                                          mpisppy/spbase.py:219-253, spopt.py:805-836 -> phgpu_bundle_*
  *   - the per-batch moments of the MMW gap estimators and of zhat4xhat
  *                                          mpisppy/confidence_intervals/ciutils.py:400-415 -> phgpu_gap_moments
  *   - APH's projective step, dispatch and partial solve loop (Update_y, Compute_Averages,
@@ -842,6 +844,62 @@ int phgpu_ef_step(phgpu_handle h, int32_t stage, const double* rsum, const doubl
  * test passed, else PHGPU_ITER_LIMIT, iters the interior-point iterations.  z [nn] device, may be NULL. */
 int phgpu_ef_export(phgpu_handle h, double* x, double* y, double* obj, double* bound, int32_t* status,
                     int32_t* iters, double* z, void* stream);
+
+/* Bundles (spbase.py:219-253, spopt.py:805-836): the local scenarios in G contiguous segments, each
+ * the extensive form of its scenarios with the probabilities p_s / p_B, all solved at once by the
+ * interior point above in a segmented form: every segment has its own z, Schur
+ * complement, mu, step lengths and termination.  The PH terms enter through the nonants' cost and
+ * diagonal; a solve reads the handle's W, rho, xbar and W_on / prox_on (phgpu_set_ph_state).  A
+ * segment never spans two ranks, so nothing is reduced over the ranks.  All entries are ordered on
+ * the stream, none synchronises, the same input gives the same bits.  An iteration is, per
+ * right-hand side, phgpu_bundle_schur -> phgpu_bundle_direction -> phgpu_bundle_step.
+ *
+ * phgpu_bundle_init: allocate the store (the handle's; freed by phgpu_destroy or another init).
+ * HOST arrays: seg_start [G + 1] (0 = seg_start[0] < ... < seg_start[G] = S), zlb < zub [G * nn] the
+ * nonants' tightest bounds over each segment, ncomp [G] the finite bounds of each segment's
+ * extensive form (z's included), cmax [G] its max |c|.  tol: the relative KKT tolerance; ztol: a
+ * segment is over when its residuals are at most tol AND the predictor's step of z is at most
+ * ztol (1 + max |z|) (the residuals bound the objective, not z: DESIGN.md 3.22); qp: 1 if
+ * any q is set (a solve with prox_on takes a common step in any case).  The limits and refusals
+ * of phgpu_ef_init hold (-3 shared-matrix handle or more than two stages; -1 nn or m > 64, a
+ * segment's nonant without an interior). */
+int phgpu_bundle_init(phgpu_handle h, int32_t G, const int32_t* seg_start, const double* zlb, const double* zub,
+                      const double* ncomp, const double* cmax, double tol, double ztol, int32_t qp, void* stream);
+
+/* A cold start of every segment: per scenario the solve's cost c + W_on W - prox_on rho xbar and
+ * diagonal q + prox_on rho on the nonant columns, the lanes' starting iterate; per segment cz_B =
+ * sum_s (p_s / p_B) of that cost, qz_B likewise (sums in index order), z inside its bounds, its
+ * duals, and the control scalars zeroed. */
+int phgpu_bundle_start(phgpu_handle h, void* stream);
+
+/* The scenario pass (phgpu_ef_schur's) and the segmented reduction of its terms: one thread per
+ * (value, segment) adds the segment's scenarios in index order -- no atomics, the same bits on
+ * every run.  Optional device copies for inspection (NULL: none): rsum [G][nn (nn + 1) / 2 + 2 nn +
+ * 2] and rmax [G][2] in phgpu_ef_schur's layout per segment, terms [values][S] what the lanes gave. */
+int phgpu_bundle_schur(phgpu_handle h, int32_t stage, double* rsum, double* rmax, double* terms, void* stream);
+
+/* One wave per segment: its Schur complement in LDS, its factor and the solve for dz, at stage 0
+ * followed by the segment's test; then the direction pass and its segmented reduction.  A segment that has
+ * passed its test is left alone by every later call; one whose mu or direction is not finite is
+ * stopped with the iterate it had (status PHGPU_ITER_LIMIT).
+ *   info: double[8], device or host-mapped pinned memory, stored at stage 0 only: {n, segments
+ *   still iterating, the worst primal, dual and gap residual among them, segments stopped on a
+ *   number that is not finite, the largest iteration count, n again (stored last)}, n counting the
+ *   records since phgpu_bundle_init. */
+int phgpu_bundle_direction(phgpu_handle h, int32_t stage, double* info, void* stream);
+
+/* One thread per segment: phgpu_ef_step's control step; then the lanes keep the affine direction
+ * (stage 0) or step (stage 1). */
+int phgpu_bundle_step(phgpu_handle h, int32_t stage, void* stream);
+
+/* The segments' iterates as a solve's outputs, with the meaning phgpu_solve gives them under the
+ * same W_on / prox_on: x with the segment's z in the nonant columns (bitwise equal within a
+ * segment), y [m*S] (may be NULL) the scenario's row duals over p_s / p_B, obj [S] the scenario's
+ * objective with its PH terms, bound = obj (sum_s p_s bound[s] over a segment is p_B times the
+ * segment's objective), status PHGPU_OPTIMAL where the segment passed its test, else
+ * PHGPU_ITER_LIMIT, iters the segment's interior-point iterations. */
+int phgpu_bundle_export(phgpu_handle h, double* x, double* y, double* obj, double* bound, int32_t* status,
+                        int32_t* iters, void* stream);
 
 /* Free the workspace and the handle. */
 int phgpu_destroy(phgpu_handle h);

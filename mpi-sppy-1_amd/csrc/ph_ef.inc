@@ -24,7 +24,10 @@ enum ef_ctl {
     EC_IT = 0, EC_DONE, EC_MU, EC_SIGMU, EC_AP, EC_AD, EC_COMP, EC_NCOMP, EC_CMAX, EC_TOL, EC_QP, EC_PRES, EC_DRES,
     EC_GAP, EC_OBJ, EC_HIST /* 6 */, EC_END = EC_HIST + 6
 };
-static_assert(EC_END <= EF_CTL, "ef_ctl");
+// behind them, in a segment's record (bundles): the tolerances of the segment's own test (ef_seg_test)
+#define EC_SEG_TOL EC_END
+#define EC_SEG_ZTOL (EC_END + 1)
+static_assert(EC_SEG_ZTOL < EF_CTL, "ef_ctl");
 
 struct ef_store {
     int nn, m, n, ntri, ld, nplanes;
@@ -567,6 +570,108 @@ EF_FN void ef_export_lane(const ph_data& st, const ef_store& E, int64_t s, doubl
     status[s] = E.ctl[EC_DONE] == 1.0 ? PHGPU_OPTIMAL : PHGPU_ITER_LIMIT;
     iters[s] = (int32_t)E.ctl[EC_IT];
 }
+// ------------------------------------------------------------------ segments (bundles; DESIGN.md 3.22)
+// The local scenarios in G contiguous segments, each an extensive form of its own: G copies of
+// the zd block, of C and of ctl, segment-major.  A segment's view of the store offsets the three;
+// every function above then runs on it unchanged.  The ph_data the lanes get is a view too: prob
+// is the conditional probability p_s / p_B, c and q carry the PH terms on the nonant columns.
+#define EF_ZD_LEN(E) ((size_t)(EZ_N + 1) * (E).nn)
+EF_FN ef_store ef_seg_view(const ef_store& E, int64_t g) {
+    ef_store V = E;
+    V.zd = E.zd + (size_t)g * EF_ZD_LEN(E);
+    V.C = E.C + (size_t)g * E.nn * E.ld;
+    V.ctl = E.ctl + (size_t)g * EF_CTL;
+    return V;
+}
+
+// A segment's start (V its view, scenarios s0 .. s1 - 1): cz, qz summed in index order from the
+// view's c, q and prob, z inside its bounds (zlb, zub stay as set at init), its duals, no
+// direction; the control scalars zeroed but for the static ones (ncomp, cmax, tol).
+EF_FN void ef_seg_start(const ph_data& st, const ef_store& V, int64_t s0, int64_t s1, bool qp) {
+    const int64_t S = st.S;
+    const int nn = V.nn;
+    const double *zlb = EF_Z(V, EZ_LB), *zub = EF_Z(V, EZ_UB);
+    bool anyq = qp;
+    for (int k = 0; k < nn; ++k) {
+        const int j = st.nonant_col[k];
+        double cz = 0.0, qz = 0.0;
+        for (int64_t s = s0; s < s1; ++s) {
+            cz += st.prob[s] * st.c[IX(j)];
+            qz += st.prob[s] * (st.q ? st.q[IX(j)] : 0.0);
+        }
+        anyq = anyq || qz != 0.0;
+        EF_Z(V, EZ_C)[k] = cz;
+        EF_Z(V, EZ_Q)[k] = qz;
+        EF_Z(V, EZ_Z)[k] = ef_inside(zlb[k], zub[k]);
+        EF_Z(V, EZ_ZL)[k] = isfinite(zlb[k]) ? 1.0 + fabs(cz) : 0.0;
+        EF_Z(V, EZ_ZU)[k] = isfinite(zub[k]) ? 1.0 + fabs(cz) : 0.0;
+        EF_Z(V, EZ_DZ)[k] = EF_Z(V, EZ_DZA)[k] = EF_Z(V, EZ_N)[k] = 0.0;
+    }
+    for (int e = 0; e < EF_CTL; ++e)
+        if (e != EC_NCOMP && e != EC_CMAX && e != EC_TOL && e != EC_SEG_TOL && e != EC_SEG_ZTOL) V.ctl[e] = 0.0;
+    V.ctl[EC_QP] = anyq ? 1.0 : 0.0;
+}
+
+// EC_DONE of a segment: 0 iterating, 1 its iterate passed the test, EF_SEG_STOPPED it was stopped
+// because a number of its iteration is not finite (it keeps the iterate it had; not OPTIMAL)
+#define EF_SEG_STOPPED 2.0
+// A segment's own test, by one thread after ef_solve_core(stage 0) and ef_seg_refine.  The core's
+// test is switched off (ctl[EC_TOL] < 0), so it has stored the residuals of the iterate and gone on
+// to the predictor's dz.  The segment is over when the three residuals are at most tol AND the
+// predictor's step of z is at most ztol (1 + max |z|): near the solution that Newton step is the
+// distance of z from it, which the residuals do not bound (the gap bounds the objective, and z only
+// by its square root; DESIGN.md 3.22).  A complementarity that is not finite stops the segment.
+EF_FN void ef_seg_test(const ef_store& V) {
+    if (V.ctl[EC_DONE] != 0.0) return;
+    if (!isfinite(V.ctl[EC_MU])) {
+        V.ctl[EC_DONE] = EF_SEG_STOPPED;
+        return;
+    }
+    const double tol = V.ctl[EC_SEG_TOL];
+    if (!(V.ctl[EC_PRES] <= tol && V.ctl[EC_DRES] <= tol && V.ctl[EC_GAP] <= tol)) return;
+    const double *z = EF_Z(V, EZ_Z), *dz = EF_Z(V, EZ_DZ);
+    double zm = 0.0, dm = 0.0;
+    for (int k = 0; k < V.nn; ++k) {
+        zm = fmax(zm, fabs(z[k]));
+        dm = fmax(dm, fabs(dz[k]));
+    }
+    if (dm <= V.ctl[EC_SEG_ZTOL] * (1.0 + zm)) V.ctl[EC_DONE] = 1.0;
+}
+// After a segment's ef_solve_core (M: the Cholesky factor and behind it nn doubles, as the core
+// leaves them): dz corrected for the regularisation of C.  The core solves (C + R) dz = rhs with
+// R = EF_REG diag(C); the exact dz is dz + C^-1 R dz, to first order dz + (C + R)^-1 R dz: one more
+// solve on the same factor, with diag(C + R) read off the factor's rows.  Without it R dz is left in
+// z's stationarity row at every step; C grows like 1 / mu, and a bundle's dual residual then stalls
+// above 1e-10 (1 + max |c|) (DESIGN.md 3.22).  A pivot the factorisation dropped takes no part.
+EF_FN void ef_seg_refine(const ef_store& V, double* M) {
+    if (V.ctl[EC_DONE] != 0.0) return;  // (the same for every thread: thread 0 stops a segment after this)
+    const int nn = V.nn, ld = V.ld;
+    double* r = M + (size_t)nn * ld;
+    double* dz = EF_Z(V, EZ_DZ);
+    LS_SYNC();
+    for (int k = LS_TID; k < nn; k += LS_NT) {
+        double d = 0.0;
+        for (int j = 0; j <= k; ++j) d += M[k * ld + j] * M[k * ld + j];
+        r[k] = M[k * ld + k] < 1e60 ? (EF_REG / (1.0 + EF_REG)) * d * dz[k] : 0.0;
+    }
+    LS_SYNC();
+    ls_fwd(M, nn, ld, r);
+    ls_bwd(M, nn, ld, r);
+    for (int k = LS_TID; k < nn; k += LS_NT) dz[k] += r[k];
+}
+// a segment's control step: ef_ctrl_core unless the direction's sums or dz are not finite, which
+// stops the segment before the step is taken (every later pass returns at its first instruction)
+EF_FN void ef_seg_ctrl(const ef_store& V, int stage, const double* rsum, const double* rmax) {
+    if (V.ctl[EC_DONE] != 0.0) return;
+    bool ok = isfinite(rsum[0]) && isfinite(rsum[1]) && isfinite(rsum[2]) && isfinite(rmax[0]) && isfinite(rmax[1]);
+    const double* dz = EF_Z(V, EZ_DZ);
+    for (int k = 0; k < V.nn; ++k) ok = ok && isfinite(dz[k]);
+    if (!ok) {
+        V.ctl[EC_DONE] = EF_SEG_STOPPED;
+        return;
+    }
+    ef_ctrl_core(V, stage, rsum, rmax);
+}
 #endif  // __HIPCC__ || EF_HOST
 
 #if defined(__HIPCC__) && !defined(EF_HOST)
@@ -628,5 +733,159 @@ k_ef_solve(ef_store E, int stage, const double* __restrict__ rsum, const double*
 __global__ void __launch_bounds__(WAVE)
 k_ef_ctrl(ef_store E, int stage, const double* __restrict__ rsum, const double* __restrict__ rmax) {
     if (threadIdx.x == 0) ef_ctrl_core(E, stage, rsum, rmax);
+}
+
+// ------------------------------------------------------------------ segments: kernels (DESIGN.md 3.22)
+// what the segmented kernels read besides the store: the segments, the per-solve copies of the
+// cost and the diagonal with the PH terms, and each segment's sums and maxima
+struct ef_segs {
+    int G, nsum0;
+    const int32_t *seg_start, *seg_of;  // [G + 1], [S]
+    double *cprob, *ceff, *qeff;        // [S], [n][S], [n][S]
+    double *rsum, *rmax;                // [G][nsum0], [G][2]
+};
+#define EF_SEG_LANE(call)                                             \
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; \
+    if (s < st.S) {                                                   \
+        const ef_store V = ef_seg_view(E, B.seg_of[s]);               \
+        call;                                                         \
+    }
+
+// The solve's cost and diagonal per scenario (raw: the handle's own data; W, rho, xbar [nn][S]):
+// c + W_on W - prox_on rho xbar and q + prox_on rho on the nonant columns; then the lane's start.
+// st is the view (prob = B.cprob, c = B.ceff, q = B.qeff).
+__global__ void __launch_bounds__(EF_T)
+k_bd_start(ph_data st, ef_store E, ef_segs B, const double* __restrict__ c0, const double* __restrict__ q0,
+           const double* __restrict__ W, const double* __restrict__ rho, const double* __restrict__ xbar, int W_on,
+           int prox_on) {
+    const int64_t S = st.S;
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    for (int j = 0; j < st.n; ++j) {
+        const int k = st.nonant_slot[j];
+        double c = c0[IX(j)], q = q0 ? q0[IX(j)] : 0.0;
+        if (k >= 0) {
+            if (W_on) c += W[IX(k)];
+            if (prox_on) {
+                c -= rho[IX(k)] * xbar[IX(k)];
+                q += rho[IX(k)];
+            }
+        }
+        B.ceff[IX(j)] = c;
+        B.qeff[IX(j)] = q;
+    }
+    ef_start_lane(st, ef_seg_view(E, B.seg_of[s]), s);
+}
+// one thread per segment, after k_bd_start
+__global__ void __launch_bounds__(EF_T) k_bd_zstart(ph_data st, ef_store E, ef_segs B, int qp) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < B.G) ef_seg_start(st, ef_seg_view(E, g), B.seg_start[g], B.seg_start[g + 1], qp != 0);
+}
+__global__ void __launch_bounds__(EF_T) k_bd_schur(ph_data st, ef_store E, ef_segs B, int stage) {
+    EF_SEG_LANE(ef_schur_lane(st, V, s, stage));
+}
+__global__ void __launch_bounds__(EF_T) k_bd_direction(ph_data st, ef_store E, ef_segs B, int stage) {
+    EF_SEG_LANE(ef_direction_lane(st, V, s, stage));
+}
+__global__ void __launch_bounds__(EF_T) k_bd_keep(ph_data st, ef_store E, ef_segs B) { EF_SEG_LANE(ef_keep_lane(st, V, s)); }
+__global__ void __launch_bounds__(EF_T) k_bd_step(ph_data st, ef_store E, ef_segs B) { EF_SEG_LANE(ef_step_lane(st, V, s)); }
+
+// The segmented reduction: one THREAD per (plane, segment), the segment fastest over the threads;
+// it walks its segment's scenarios of its plane in index order, so the order of addition is fixed
+// and there are no atomics.  A segment that is over is skipped.
+__global__ void __launch_bounds__(GR_T) k_bd_reduce(ef_store E, ef_segs B, int64_t S, int nsum, int nmax) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)(nsum + nmax) * B.G) return;
+    const int b = (int)(t / B.G), g = (int)(t % B.G);
+    if (E.ctl[(size_t)g * EF_CTL + EC_DONE] != 0.0) return;
+    const bool mx = b >= nsum;
+    double acc = 0.0;
+    for (int64_t s = B.seg_start[g]; s < B.seg_start[g + 1]; ++s) {
+        const double v = E.terms[IX(b)];
+        acc = mx ? fmax(acc, v) : acc + v;
+    }
+    if (mx) B.rmax[(size_t)g * 2 + (b - nsum)] = acc;
+    else B.rsum[(size_t)g * B.nsum0 + b] = acc;
+}
+
+// One wave per segment: C in LDS (dynamic, the only shared memory of the kernel, so its base is
+// aligned; the flag sits behind the matrix and the right-hand side).  info8 [G][8]: the cores'
+// records, device memory.
+__global__ void __launch_bounds__(WAVE) k_bd_solve(ef_store E, ef_segs B, int stage, double* __restrict__ info8) {
+    const int g = blockIdx.x;
+    const ef_store V = ef_seg_view(E, g);
+    int* done = (int*)(ef_dyn + (size_t)E.nn * E.ld + E.nn);
+    ef_solve_core(V, stage, B.rsum + (size_t)g * B.nsum0, B.rmax + (size_t)g * 2, info8 + (size_t)g * 8, ef_dyn, done);
+    ef_seg_refine(V, ef_dyn);
+    __syncthreads();  // (dz is whole before one thread reads it)
+    if (stage == 0 && threadIdx.x == 0) ef_seg_test(V);
+}
+// one thread per segment
+__global__ void __launch_bounds__(EF_T) k_bd_ctrl(ef_store E, ef_segs B, int stage) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < B.G) ef_seg_ctrl(ef_seg_view(E, g), stage, B.rsum + (size_t)g * B.nsum0, B.rmax + (size_t)g * 2);
+}
+
+// The host's record of an iteration (one workgroup, after the stage-0 solve; info: 8 doubles,
+// host-mapped): {seq, segments still iterating, the worst primal, dual and gap residual among
+// them, segments stopped on a number that is not finite, the largest iteration count, seq again
+// (stored last)}.  The count by an integer atomic in LDS, the maxima in a fixed order.
+__global__ void __launch_bounds__(GR_T) k_bd_record(ef_store E, int G, double seq, double* __restrict__ info) {
+    __shared__ double red[4][GR_T / WAVE];
+    __shared__ int cnt[2];
+    if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    double v[4] = {0.0, 0.0, 0.0, 0.0};
+    int open = 0, stopped = 0;
+    for (int g = threadIdx.x; g < G; g += GR_T) {
+        const double* ctl = E.ctl + (size_t)g * EF_CTL;
+        v[3] = fmax(v[3], ctl[EC_IT]);
+        if (ctl[EC_DONE] == EF_SEG_STOPPED) ++stopped;
+        if (ctl[EC_DONE] != 0.0) continue;
+        ++open;
+        v[0] = fmax(v[0], ctl[EC_PRES]);
+        v[1] = fmax(v[1], ctl[EC_DRES]);
+        v[2] = fmax(v[2], ctl[EC_GAP]);
+    }
+    if (open) atomicAdd(&cnt[0], open);
+    if (stopped) atomicAdd(&cnt[1], stopped);
+    for (int u = 0; u < 4; ++u) {
+        const double w = wave_max(v[u]);
+        if ((threadIdx.x & (WAVE - 1)) == 0) red[u][threadIdx.x / WAVE] = w;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int u = 0; u < 4; ++u) {
+            double t = 0.0;
+            for (int w = 0; w < GR_T / WAVE; ++w) t = fmax(t, red[u][w]);
+            v[u] = t;
+        }
+        info[1] = (double)cnt[0];
+        info[2] = v[0];
+        info[3] = v[1];
+        info[4] = v[2];
+        info[5] = (double)cnt[1];
+        info[6] = v[3];
+        info[7] = seq;
+        info[0] = seq;
+    }
+}
+
+// The segments' iterates as a solve's outputs: ef_export_lane on the view (its c and q hold the PH
+// terms), plus the prox term's constant; bound = obj, so that sum_s p_s bound[s] over a segment is
+// p_B times the segment's objective.
+__global__ void __launch_bounds__(EF_T)
+k_bd_export(ph_data st, ef_store E, ef_segs B, const double* __restrict__ rho, const double* __restrict__ xbar,
+            int prox_on, double* __restrict__ x, double* __restrict__ y, double* __restrict__ obj,
+            double* __restrict__ bound, int32_t* __restrict__ status, int32_t* __restrict__ iters) {
+    const int64_t S = st.S;
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    ef_export_lane(st, ef_seg_view(E, B.seg_of[s]), s, x, y, obj, bound, status, iters);
+    double o = obj[s];
+    if (prox_on)
+        for (int k = 0; k < st.nn; ++k) o += 0.5 * rho[IX(k)] * xbar[IX(k)] * xbar[IX(k)];
+    obj[s] = o;
+    bound[s] = o;
 }
 #endif

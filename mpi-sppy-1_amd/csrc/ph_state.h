@@ -20,6 +20,7 @@ struct fwph_store;  // ph_fwph.inc: the FWPH column store of a handle
 struct sel_state;   // ph_aph.inc: the workspace of phgpu_select_smallest
 struct ls_store;    // ph_lshaped.inc: the cut store and master of the L-shaped method
 struct ef_store;    // ph_ef.inc: the iterate and work space of the extensive-form interior point
+struct bd_store;    // phgpu.hip: the segmented form of it, one extensive form per bundle
 struct ph_ws {      // a reduction's device workspace: partials, and node tags or a ticket counter
     double* part;
     int32_t* tag;
@@ -248,6 +249,9 @@ struct phgpu_state : pdhg_view {
     // phgpu_ef_*: the extensive-form interior point's iterate, factors and work space (host record
     // of its device buffers; null until phgpu_ef_init)
     ef_store* ef;
+    // phgpu_bundle_*: the segmented extensive-form interior point (one segment per bundle; host
+    // record of its device buffers; null until phgpu_bundle_init)
+    bd_store* bd;
     // phgpu_gap_moments: two slots of GM_NV partials per wave (its head and its tail run) and
     // their segment tags [2 * nwaves], allocated at its first call
     ph_ws gm;

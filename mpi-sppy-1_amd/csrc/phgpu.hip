@@ -3326,6 +3326,237 @@ extern "C" int phgpu_ef_export(phgpu_handle h, double* x, double* y, double* obj
     return 0;
 }
 
+// ------------------------------------------------------------------ bundles: the segmented form (ph_ef.inc)
+// One extensive form per contiguous segment of the local scenarios (spbase.py:219-253,
+// spopt.py:805-836), all solved at once.
+struct bd_store {
+    ef_store E;  // zd, C, ctl: G copies, segment-major
+    ef_segs B;
+    int32_t *seg_start, *seg_of;
+    double* info8;  // [G][8]: the cores' own records
+    int qp;
+    double seq;  // records stored so far
+};
+
+static void bd_release(phgpu_state* h) {
+    bd_store* D = h->bd;
+    if (!D) return;
+    ef_store* E = &D->E;
+    dfree(h, &E->x); dfree(h, &E->zl); dfree(h, &E->zu); dfree(h, &E->dx); dfree(h, &E->dxa); dfree(h, &E->D);
+    dfree(h, &E->w); dfree(h, &E->vl); dfree(h, &E->vu); dfree(h, &E->y); dfree(h, &E->dw); dfree(h, &E->dwa);
+    dfree(h, &E->dy); dfree(h, &E->dya); dfree(h, &E->g); dfree(h, &E->wk); dfree(h, &E->rp); dfree(h, &E->E);
+    dfree(h, &E->fac); dfree(h, &E->terms); dfree(h, &E->zd); dfree(h, &E->C); dfree(h, &E->ctl);
+    dfree(h, &D->B.cprob); dfree(h, &D->B.ceff); dfree(h, &D->B.qeff); dfree(h, &D->B.rsum); dfree(h, &D->B.rmax);
+    dfree(h, &D->seg_start); dfree(h, &D->seg_of); dfree(h, &D->info8);
+    delete D;
+    h->bd = nullptr;
+}
+
+// the lanes' view of the problem: conditional probabilities, the solve's cost and diagonal
+static inline ph_data bd_view(const phgpu_state* h, const bd_store& D) {
+    ph_data v = *h;
+    v.prob = D.B.cprob;
+    v.c = D.B.ceff;
+    v.q = D.B.qeff;
+    return v;
+}
+
+extern "C" int phgpu_bundle_init(phgpu_handle h, int32_t G, const int32_t* seg_start, const double* zlb, const double* zub,
+                                 const double* ncomp, const double* cmax, double tol, double ztol, int32_t qp, void* stream) {
+    if (!h) return set_err(-1, "null handle");
+    if (!h->scen_set) return set_err(-1, "phgpu_bundle_init: no scenario data yet");
+    if (h->shared) return set_err(-3, "phgpu_bundle_init: a shared-matrix handle is not served");
+    if (h->depth != 1 || h->num_nodes != 1)
+        return set_err(-3, "phgpu_bundle_init: two-stage handles only (depth %d, %d nodes)", h->depth, h->num_nodes);
+    if (h->nn < 1 || h->nn > EF_NN_MAX || h->m < 1 || h->m > EF_M_MAX)
+        return set_err(-1, "phgpu_bundle_init: nn %d (1..%d), m %d (1..%d)", h->nn, EF_NN_MAX, h->m, EF_M_MAX);
+    if (!seg_start || !zlb || !zub || !ncomp || !cmax) return set_err(-1, "null argument");
+    if (G < 1 || (int64_t)G > h->S || !(tol > 0.0) || !(ztol > 0.0))
+        return set_err(-1, "phgpu_bundle_init: %d segments, tol %g, ztol %g", (int)G, tol, ztol);
+    if (seg_start[0] != 0 || (int64_t)seg_start[G] != h->S)
+        return set_err(-1, "phgpu_bundle_init: the segments span [%d, %d), not the %lld local scenarios", (int)seg_start[0],
+                       (int)seg_start[G], (long long)h->S);
+    const int nn = h->nn, m = h->m, n = h->n;
+    for (int g = 0; g < G; ++g) {
+        if (seg_start[g + 1] <= seg_start[g]) return set_err(-1, "phgpu_bundle_init: segment %d is empty", g);
+        if (!(ncomp[g] >= 1.0) || !(cmax[g] >= 0.0))
+            return set_err(-1, "phgpu_bundle_init: segment %d: ncomp %g, cmax %g", g, ncomp[g], cmax[g]);
+        for (int k = 0; k < nn; ++k) {
+            const double lo = zlb[(size_t)g * nn + k], hi = zub[(size_t)g * nn + k];
+            if (!(lo < hi) || lo == INFINITY || hi == -INFINITY)
+                return set_err(-1, "phgpu_bundle_init: segment %d: nonant %d has bounds [%g, %g] (no interior)", g, k, lo, hi);
+        }
+    }
+    FLUSH_STEP(h);
+    hipStream_t st = (hipStream_t)stream;
+    if (h->bd) {
+        HIPCHK(hipStreamSynchronize(st));  // (nothing of the old store may be in flight)
+        bd_release(h);
+    }
+    bd_store* D = new (std::nothrow) bd_store();
+    if (!D) return set_err(-3, "out of host memory");
+    memset(D, 0, sizeof(*D));
+    h->bd = D;
+    ef_store* E = &D->E;
+    E->nn = nn; E->m = m; E->n = n; E->ntri = nn * (nn + 1) / 2; E->ld = nn | 1;
+    E->nplanes = ef_nsum0(*E) + 2;
+    D->B.G = G;
+    D->B.nsum0 = ef_nsum0(*E);
+    D->qp = qp ? 1 : 0;
+    const size_t S = (size_t)h->S;
+    int rc = 0;
+    for (double** p : {&E->x, &E->zl, &E->zu, &E->dx, &E->dxa, &E->D, &D->B.ceff, &D->B.qeff})
+        if (!rc) rc = dalloc(h, p, (size_t)n * S);
+    for (double** p : {&E->w, &E->vl, &E->vu, &E->y, &E->dw, &E->dwa, &E->dy, &E->dya, &E->g, &E->wk, &E->rp, &E->E})
+        if (!rc) rc = dalloc(h, p, (size_t)m * S);
+    if (!rc) rc = dalloc(h, &E->fac, (size_t)(m * (m + 1) / 2) * S);
+    if (!rc) rc = dalloc(h, &E->terms, (size_t)E->nplanes * S);
+    if (!rc) rc = dalloc(h, &E->C, (size_t)G * nn * E->ld);
+    if (!rc) rc = dalloc(h, &D->B.rsum, (size_t)G * D->B.nsum0);
+    if (!rc) rc = dalloc(h, &D->B.rmax, (size_t)G * 2);
+    if (!rc) rc = dalloc(h, &D->info8, (size_t)G * 8);
+    // per segment: the static part of zd (the bounds) and of ctl; the conditional probabilities
+    std::vector<double> zd((size_t)G * EF_ZD_LEN(*E), 0.0), ctl((size_t)G * EF_CTL, 0.0), prob(S), cprob(S);
+    std::vector<int32_t> seg_of(S);
+    // (a failure from here on gives the half-built store back: no later entry may find it)
+#define BD_CHK(call)                                                                                          \
+    do {                                                                                                      \
+        hipError_t e_ = (call);                                                                               \
+        if (e_ != hipSuccess) {                                                                               \
+            bd_release(h);                                                                                    \
+            return set_err(-2, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__);  \
+        }                                                                                                     \
+    } while (0)
+    if (!rc) BD_CHK(hipMemcpy(prob.data(), h->prob, S * sizeof(double), hipMemcpyDeviceToHost));
+    for (int g = 0; g < G && !rc; ++g) {
+        double* z = zd.data() + (size_t)g * EF_ZD_LEN(*E);
+        for (int k = 0; k < nn; ++k) {
+            z[(size_t)EZ_LB * nn + k] = zlb[(size_t)g * nn + k];
+            z[(size_t)EZ_UB * nn + k] = zub[(size_t)g * nn + k];
+        }
+        double* c = ctl.data() + (size_t)g * EF_CTL;
+        c[EC_NCOMP] = ncomp[g]; c[EC_CMAX] = cmax[g];
+        c[EC_TOL] = -1.0;  // (the core's own test is off: ef_seg_test decides, after the predictor's dz)
+        c[EC_SEG_TOL] = tol; c[EC_SEG_ZTOL] = ztol;
+        double pb = 0.0;
+        for (int32_t s = seg_start[g]; s < seg_start[g + 1]; ++s) pb += prob[s];
+        if (!(pb > 0.0)) {
+            bd_release(h);
+            return set_err(-1, "phgpu_bundle_init: segment %d has probability %g", g, pb);
+        }
+        for (int32_t s = seg_start[g]; s < seg_start[g + 1]; ++s) {
+            cprob[s] = prob[s] / pb;
+            seg_of[s] = g;
+        }
+    }
+    if (!rc) rc = ls_upload(h, &E->zd, zd.data(), zd.size());
+    if (!rc) rc = ls_upload(h, &E->ctl, ctl.data(), ctl.size());
+    if (!rc) rc = ls_upload(h, &D->B.cprob, cprob.data(), cprob.size());
+    if (!rc) rc = ls_upload(h, &D->seg_start, seg_start, (size_t)G + 1);
+    if (!rc) rc = ls_upload(h, &D->seg_of, seg_of.data(), seg_of.size());
+    if (rc) {
+        bd_release(h);
+        return rc;
+    }
+    D->B.seg_start = D->seg_start;
+    D->B.seg_of = D->seg_of;
+    BD_CHK(hipMemsetAsync(E->terms, 0, (size_t)E->nplanes * S * sizeof(double), st));
+    BD_CHK(hipMemsetAsync(D->B.rsum, 0, (size_t)G * D->B.nsum0 * sizeof(double), st));
+    BD_CHK(hipMemsetAsync(D->B.rmax, 0, (size_t)G * 2 * sizeof(double), st));
+    BD_CHK(hipMemsetAsync(D->info8, 0, (size_t)G * 8 * sizeof(double), st));
+#undef BD_CHK
+    return 0;
+}
+
+#define BD_READY(h, who, stage)                                                              \
+    do {                                                                                     \
+        if (!(h)) return set_err(-1, "null handle");                                         \
+        if (!(h)->bd) return set_err(-1, who ": phgpu_bundle_init has not run");             \
+        if ((stage) != 0 && (stage) != 1) return set_err(-1, who ": stage %d", (int)(stage)); \
+        FLUSH_STEP(h);                                                                       \
+    } while (0)
+#define BD_GRID(h) dim3((unsigned)(((h)->S + EF_T - 1) / EF_T))
+#define BD_SEG_GRID(D) dim3((unsigned)(((D).B.G + EF_T - 1) / EF_T))
+
+// every solve is a cold start from the handle's W, rho, x̄ and its W_on / prox_on switches
+extern "C" int phgpu_bundle_start(phgpu_handle h, void* stream) {
+    BD_READY(h, "phgpu_bundle_start", 0);
+    if ((h->W_on || h->prox_on) && (!h->W || !h->rho || !h->xbar))
+        return set_err(-1, "phgpu_bundle_start: W_on / prox_on without phgpu_set_ph_state's arrays");
+    hipStream_t st = (hipStream_t)stream;
+    const bd_store& D = *h->bd;
+    const ph_data v = bd_view(h, D);
+    hipLaunchKernelGGL(k_bd_start, BD_GRID(h), dim3(EF_T), 0, st, v, D.E, D.B, (const double*)h->c, (const double*)h->q,
+                       h->W, h->rho, h->xbar, h->W_on, h->prox_on);
+    hipLaunchKernelGGL(k_bd_zstart, BD_SEG_GRID(D), dim3(EF_T), 0, st, v, D.E, D.B, (D.qp || h->prox_on) ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static void bd_reduce(phgpu_state* h, const bd_store& D, int nsum, int nmax, hipStream_t st) {
+    const int64_t nt = (int64_t)(nsum + nmax) * D.B.G;
+    hipLaunchKernelGGL(k_bd_reduce, dim3((unsigned)((nt + GR_T - 1) / GR_T)), dim3(GR_T), 0, st, D.E, D.B, h->S, nsum, nmax);
+}
+
+extern "C" int phgpu_bundle_schur(phgpu_handle h, int32_t stage, double* rsum, double* rmax, double* terms, void* stream) {
+    BD_READY(h, "phgpu_bundle_schur", stage);
+    hipStream_t st = (hipStream_t)stream;
+    const bd_store& D = *h->bd;
+    hipLaunchKernelGGL(k_bd_schur, BD_GRID(h), dim3(EF_T), 0, st, bd_view(h, D), D.E, D.B, (int)stage);
+    bd_reduce(h, D, stage == 0 ? D.B.nsum0 : D.E.nn, stage == 0 ? 2 : 0, st);
+    HIPCHK(hipGetLastError());
+    const size_t G = (size_t)D.B.G;
+    if (rsum) HIPCHK(hipMemcpyAsync(rsum, D.B.rsum, G * D.B.nsum0 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (rmax) HIPCHK(hipMemcpyAsync(rmax, D.B.rmax, G * 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (terms)
+        HIPCHK(hipMemcpyAsync(terms, D.E.terms, (size_t)D.E.nplanes * (size_t)h->S * sizeof(double), hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+extern "C" int phgpu_bundle_direction(phgpu_handle h, int32_t stage, double* info, void* stream) {
+    BD_READY(h, "phgpu_bundle_direction", stage);
+    if (stage == 0 && !info) return set_err(-1, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    bd_store& D = *h->bd;
+    const size_t lds = (((size_t)D.E.nn * D.E.ld + D.E.nn + 1) * sizeof(double) + 15) & ~(size_t)15;
+    hipLaunchKernelGGL(k_bd_solve, dim3((unsigned)D.B.G), dim3(WAVE), lds, st, D.E, D.B, (int)stage, D.info8);
+    if (stage == 0) {
+        D.seq += 1.0;
+        hipLaunchKernelGGL(k_bd_record, dim3(1), dim3(GR_T), 0, st, D.E, D.B.G, D.seq, info);
+    }
+    hipLaunchKernelGGL(k_bd_direction, BD_GRID(h), dim3(EF_T), 0, st, bd_view(h, D), D.E, D.B, (int)stage);
+    bd_reduce(h, D, 3, 2, st);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int phgpu_bundle_step(phgpu_handle h, int32_t stage, void* stream) {
+    BD_READY(h, "phgpu_bundle_step", stage);
+    hipStream_t st = (hipStream_t)stream;
+    const bd_store& D = *h->bd;
+    hipLaunchKernelGGL(k_bd_ctrl, BD_SEG_GRID(D), dim3(EF_T), 0, st, D.E, D.B, (int)stage);
+    const ph_data v = bd_view(h, D);
+    if (stage == 0) hipLaunchKernelGGL(k_bd_keep, BD_GRID(h), dim3(EF_T), 0, st, v, D.E, D.B);
+    else hipLaunchKernelGGL(k_bd_step, BD_GRID(h), dim3(EF_T), 0, st, v, D.E, D.B);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int phgpu_bundle_export(phgpu_handle h, double* x, double* y, double* obj, double* bound, int32_t* status,
+                                   int32_t* iters, void* stream) {
+    BD_READY(h, "phgpu_bundle_export", 0);
+    if (!x || !obj || !bound || !status || !iters) return set_err(-1, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    const bd_store& D = *h->bd;
+    hipLaunchKernelGGL(k_bd_export, BD_GRID(h), dim3(EF_T), 0, st, bd_view(h, D), D.E, D.B, h->rho, h->xbar, h->prox_on, x, y,
+                       obj, bound, status, iters);
+    HIPCHK(hipGetLastError());
+    h->last_stats = nullptr;  // (the statistics of this solve come from its status / iters outputs)
+    h->last_status = status;
+    h->last_iters = iters;
+    return 0;
+}
+
 #include "comm_rccl.inc"
 
 extern "C" int phgpu_destroy(phgpu_handle h) {
@@ -3337,6 +3568,7 @@ extern "C" int phgpu_destroy(phgpu_handle h) {
     delete h->fw;  // (its device buffers are in allocs)
     delete h->ls;
     delete h->ef;
+    delete h->bd;
     phgpu_owner* o = owner_of(h);  // (a deferred step that never ran is dropped with it)
     for (const dev_alloc& a : o->allocs) (void)hipFree(a.p);
     delete o;

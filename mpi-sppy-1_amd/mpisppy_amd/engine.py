@@ -1577,6 +1577,98 @@ class PHEngine:
                                             _ptr(self.status), _ptr(self.iters), _ptr(self.ef_z), self._stream()),
                    "phgpu_ef_export")
 
+    # -------------------------------------------------------------- bundles
+    def bundle_init(self, seg_start, zlb, zub, ncomp, cmax, tol, ztol, qp):
+        """The segmented interior point's store (phgpu_bundle_init): host arrays
+        seg_start [G + 1], zlb, zub [G, nn], ncomp, cmax [G]; ``tol``, ``ztol``: the bundles' test.  ``bundle_info`` is the pinned record
+        phgpu_bundle_direction stores at stage 0."""
+        self._flush_step()
+        seg = np.ascontiguousarray(seg_start, dtype=np.int32)
+        G = len(seg) - 1
+        f8 = lambda a, *s: np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(*s))  # noqa: E731
+        zlb, zub, ncomp, cmax = f8(zlb, G, self.nn), f8(zub, G, self.nn), f8(ncomp, G), f8(cmax, G)
+        hp = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+        _lib.check(self.lib.phgpu_bundle_init(self.h, G, hp(seg), hp(zlb), hp(zub), hp(ncomp), hp(cmax), float(tol),
+                                              float(ztol), int(bool(qp)), self._stream()), "phgpu_bundle_init")
+        self.bundle_G, self.bundle_seg = G, seg
+        self.bundle_nsum0 = self.nn * (self.nn + 1) // 2 + 2 * self.nn + 2
+        self.bundle_info = torch.zeros(8, dtype=torch.float64).pin_memory()
+        self._bundle_info_np = self.bundle_info.numpy()
+        self._bundle_ev = torch.cuda.Event()
+        for k in ("bundle_solve", "bundle_schur", "bundle_direction", "bundle_step"):
+            self.calls[k] = 0
+
+    def bundle_start(self):
+        """A cold start of every bundle from W, rho, x̄ and the W_on / prox_on switches."""
+        _lib.check(self.lib.phgpu_bundle_start(self.h, self._stream()), "phgpu_bundle_start")
+
+    def bundle_schur(self, stage, inspect=False):
+        """The scenario pass and the segmented reduction (phgpu_bundle_schur).  ``inspect``: device
+        copies (rsum [G, nsum0], rmax [G, 2], terms [nsum0 + 2, S]) are returned."""
+        self.calls["bundle_schur"] += 1
+        out = (None, None, None)
+        if inspect:
+            z = lambda *s: torch.zeros(*s, dtype=torch.float64, device=self.device)  # noqa: E731
+            out = (z(self.bundle_G, self.bundle_nsum0), z(self.bundle_G, 2), z(self.bundle_nsum0 + 2, self.S))
+        _lib.check(self.lib.phgpu_bundle_schur(self.h, int(stage), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), self._stream()),
+                   "phgpu_bundle_schur")
+        return out
+
+    def bundle_direction(self, stage):
+        self.calls["bundle_direction"] += 1
+        if stage == 0:
+            self._bundle_info_np[:] = np.nan
+        _lib.check(self.lib.phgpu_bundle_direction(self.h, int(stage), ctypes.c_void_p(self.bundle_info.data_ptr()),
+                                                   self._stream()), "phgpu_bundle_direction")
+        if stage == 0:
+            self._bundle_ev.record()
+
+    def bundle_step(self, stage):
+        self.calls["bundle_step"] += 1
+        _lib.check(self.lib.phgpu_bundle_step(self.h, int(stage), self._stream()), "phgpu_bundle_step")
+
+    def bundle_read(self):
+        """The iteration's one read: a wait for the last stage-0 direction call and the pinned
+        record (the test of the iterates that iteration started from)."""
+        self._bundle_ev.synchronize()
+        v = self._bundle_info_np
+        return {"open": int(v[1]), "pres": float(v[2]), "dres": float(v[3]), "gap": float(v[4]), "stopped": int(v[5]),
+                "iter": int(v[6])}
+
+    def bundle_solve(self, max_iter):
+        """phgpu_solve's counterpart with bundles: every bundle's extensive form from a cold start
+        into x, y, obj, bound, status, iters.  One read of pinned memory per interior-point
+        iteration; the loop ends when no bundle is iterating any more, or after ``max_iter``
+        iterations with a last test of the iterates.  Returns the last record and ``passes``."""
+        if getattr(self, "_xbar_pending", False):
+            self.compute_xbar()
+        self._flush_step()
+        self.calls["bundle_solve"] += 1
+        self._launch_id += 1
+        self._cur_id = self._launch_id
+        self.bundle_start()
+        r, passes = None, 0
+        for _ in range(int(max_iter)):
+            # the whole iteration is queued before the read: the record is stored by the stage-0
+            # direction call, and once no bundle iterates every later kernel returns at once
+            for stage in (0, 1):
+                self.bundle_schur(stage)
+                self.bundle_direction(stage)
+                self.bundle_step(stage)
+            r = self.bundle_read()
+            if r["open"] == 0:
+                break
+            passes += 1
+        else:
+            self.bundle_schur(0)          # the test of the last iterates (nothing steps)
+            self.bundle_direction(0)
+            r = self.bundle_read()
+        _lib.check(self.lib.phgpu_bundle_export(self.h, _ptr(self.x), _ptr(self.y if self.want_duals else None),
+                                                _ptr(self.obj), _ptr(self.bound), _ptr(self.status), _ptr(self.iters),
+                                                self._stream()), "phgpu_bundle_export")
+        r["passes"] = passes
+        return r
+
     def fix_nonants_by_node(self, table):
         """Fix every local scenario's nonants at per-node values: ``table`` is a device
         [num_nodes, nlen_max] tensor (global node order of ``node_names``); nonant k of

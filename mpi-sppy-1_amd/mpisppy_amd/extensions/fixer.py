@@ -74,6 +74,9 @@ class Fixer(Extension):
     # fixer.py:52-64
     def __init__(self, ph):
         super().__init__(ph)
+        if getattr(ph, "bundling", False):
+            raise NotImplementedError("the Fixer is not served with bundles: it fixes nonant columns, and a bundle's "
+                                      "interior point needs an interior in every nonant")
         self.ph = ph
         self.cylinder_rank = self.ph.cylinder_rank
         self.options = ph.options

@@ -30,6 +30,8 @@ from ..phbase import PHBase
 
 
 class FWPH(PHBase):
+    SERVES_BUNDLES = False     # (PHBase serves bundles; the column store is per scenario)
+
     # fwph.py:55-82
     def __init__(self, PH_options, FW_options, all_scenario_names, scenario_creator, scenario_denouement=None,
                  all_nodenames=None, mpicomm=None, scenario_creator_kwargs=None, ph_converger=None,

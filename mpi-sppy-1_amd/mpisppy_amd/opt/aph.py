@@ -38,6 +38,8 @@ def dispatch_count(n_local, dispatch_frac):
 
 
 class APH(PHBase):
+    SERVES_BUNDLES = False     # (PHBase serves bundles; APH's dispatch and list solve do not)
+
     # aph.py:69-123
     def __init__(self, options, all_scenario_names, scenario_creator, scenario_denouement=None,
                  all_nodenames=None, mpicomm=None, scenario_creator_kwargs=None, extensions=None,

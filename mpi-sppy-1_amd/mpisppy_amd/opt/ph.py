@@ -4,6 +4,7 @@ from ..phbase import PHBase
 
 class PH(PHBase):
     """PH. See PHBase for the list of args."""
+    SERVES_BUNDLES = True
 
     def ph_main(self, finalize=True):
         """PH_Prep -> Iter0 -> iterk_loop -> post_loops; returns (conv, Eobj, trivial_bound)

@@ -21,6 +21,10 @@ PH_EPS_REL = 1e-9      # the library default (phgpu_default_options), used by th
 
 
 class PHBase(SPOpt):
+    # bundles_per_rank: every solve_loop solves each bundle's extensive form; here,
+    # not only in PH, so that the Lagrangian spoke's PHBase serves them too
+    SERVES_BUNDLES = True
+
     def __init__(self, options, all_scenario_names, scenario_creator, scenario_denouement=None,
                  all_nodenames=None, mpicomm=None, scenario_creator_kwargs=None, extensions=None,
                  extension_kwargs=None, ph_converger=None, rho_setter=None,
@@ -176,7 +180,8 @@ class PHBase(SPOpt):
                         gripe=not self._iter0_eps_default, verbose=verbose, warm_start=False)
         # local scenarios whose Iter0 LP needed the relaxed re-solve below (reported by
         # bench.py next to iter0_not_optimal, and by a warning on the ranks that have any)
-        self.iter0_relaxed = self.engine.count_not_optimal() if self._iter0_eps_default else 0
+        # (with bundles bundle_tol and bundle_max_iter govern the solve: there is no relaxed re-solve)
+        self.iter0_relaxed = self.engine.count_not_optimal() if self._iter0_eps_default and not self.bundling else 0
         if self.iter0_relaxed > 0:
             print(f"WARNING (rank {self.cylinder_rank}): {self.iter0_relaxed} Iter0 LP(s) missed eps_rel "
                   f"{LP_EPS_REL:g}; every scenario is re-solved at {PH_EPS_REL:g} from its warm start",
@@ -267,6 +272,12 @@ class PHBase(SPOpt):
 
     # phbase.py:875-979
     def _speculate(self, have_ext):
+        if self.bundling:
+            if self.options.get("speculative_solve", False):
+                raise NotImplementedError("speculative_solve (the speculative solve and the PH step deferred into it) is "
+                                          "not served with bundles: a bundle solve reads the host's record every "
+                                          "interior-point iteration")
+            return False
         if not self.options.get("speculative_solve", True):
             return False
         if self.options.get("display_timing") or self.options.get("record_pdhg_iters"):
@@ -301,6 +312,9 @@ class PHBase(SPOpt):
         what the step-by-step loop's does (0.1169 against 0.1163 ms, the launch overhead
         being hidden already by the speculative solve), and its fixed cost per call is ~0.1 ms
         (DESIGN.md 3.11)."""
+        if self.bundling and self.options.get("fused_ph_loop", False):
+            raise NotImplementedError("fused_ph_loop (the fused PH loop) is not served with bundles: its one launch "
+                                      "holds the per-scenario interior point")
         if not self.options.get("fused_ph_loop", False) or self.n_proc > 1 or self.spcomm is not None:
             return False
         if have_ext or self.options.get("display_progress") or self.options.get("display_convergence_detail"):

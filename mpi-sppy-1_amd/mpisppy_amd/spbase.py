@@ -28,6 +28,10 @@ def nonleaf_nodenames(all_nodenames):
 
 
 class SPBase:
+    # A class whose solves run over bundles says so (PHBase and PH: DESIGN.md 3.22); in every
+    # other class ``bundles_per_rank`` raises NotImplementedError.
+    SERVES_BUNDLES = False
+
     def __init__(self, options, all_scenario_names, scenario_creator, scenario_denouement=None,
                  all_nodenames=None, mpicomm=None, scenario_creator_kwargs=None,
                  variable_probability=None, E1_tolerance=1e-5):
@@ -52,17 +56,37 @@ class SPBase:
             global_toc("Initializing SPBase", self.cylinder_rank == 0)
         if self.n_proc > len(self.all_scenario_names):
             raise RuntimeError("More ranks than scenarios")                 # spbase.py:94-95
-        if options.get("bundles_per_rank", 0):
-            raise NotImplementedError("bundles are outside the batched PH hot path")
+        self.bundles_per_rank = int(options.get("bundles_per_rank", 0) or 0)
+        if self.bundles_per_rank and not self.SERVES_BUNDLES:
+            raise NotImplementedError(f"bundles are outside the batched PH hot path of {type(self).__name__}: "
+                                      "PH and the Lagrangian spoke serve bundles_per_rank")
         self.bundling = False
         # rank slices (sputils.py:798-810 via spbase.py:184-216)
         self._rank_slices = rank_slices(len(self.all_scenario_names), self.n_proc)
+        if self.bundles_per_rank:
+            self._assign_bundles()
         self.local_scenario_names = [self.all_scenario_names[i]
                                      for i in self._rank_slices[self.cylinder_rank]]
         self.node_names = nonleaf_nodenames(self.all_nodenames)
         self.scenario_creator_kwargs = scenario_creator_kwargs or {}
         self._create_scenarios()
         self._use_variable_probability_setter()
+
+    # spbase.py:219-253
+    def _assign_bundles(self):
+        """``names_in_bundles[rank][bundle]``: each rank's scenarios in ``bundles_per_rank``
+        contiguous slices, ``range(int(i * avg), int((i + 1) * avg))`` with avg = scenarios of the
+        rank / bundles_per_rank."""
+        bpr = self.bundles_per_rank
+        self.names_in_bundles = {}
+        for rank, slc in enumerate(self._rank_slices):
+            slc = list(slc)
+            if len(slc) < bpr:
+                raise RuntimeError("Not enough scenarios to satisfy the bundles_per_rank requirement")
+            avg = len(slc) / bpr
+            self.names_in_bundles[rank] = {b: [self.all_scenario_names[slc[j]] for j in range(int(b * avg), int((b + 1) * avg))]
+                                           for b in range(bpr)}
+        self.bundling = True
 
     def _create_scenarios(self):
         kw = self.scenario_creator_kwargs
@@ -94,6 +118,9 @@ class SPBase:
 
     @property
     def local_subproblems(self):
+        """The scenarios, or with bundling the bundles SPOpt.subproblem_creation built."""
+        if self.bundling and getattr(self, "_bundles", None) is not None:
+            return self._bundles
         return self.local_scenarios
 
     def _options_check(self, required_options, given_options):

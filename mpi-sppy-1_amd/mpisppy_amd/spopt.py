@@ -70,7 +70,30 @@ class ScenarioView:
     def x(self):
         return self._opt.engine.host("x")[self.index]
 
+class Bundle:
+    """A bundle as a subproblem (spopt.py:805-836): the extensive form of ``scen_list`` with the
+    probabilities p_s / ``_mpisppy_probability``.  No model of it is built: it is the local
+    scenarios ``first`` .. ``last`` - 1 of the batch, one segment of the device's segmented
+    interior point.  After a solve: ``x`` [scenarios, n]."""
+
+    def __init__(self, opt, name, scen_list, first, last, prob):
+        self._opt, self.name, self._name = opt, name, name
+        self.scen_list = list(scen_list)
+        self.first, self.last = int(first), int(last)
+        self._mpisppy_probability = float(prob)
+
+    @property
+    def x(self):
+        return self._opt.engine.host("x")[self.first:self.last]
+
+
 SOLVER_NAMES = ("mi355x_pdhg", "phgpu", "mi355x")
+DEFAULT_BUNDLE_TOL = 1e-10       # 1e-8 leaves W 1.5e-4 off on farmer, 1e-12 is below what fp64 reaches (DESIGN.md 3.22)
+# a bundle is over when, besides, the predictor's step of its nonants is at most this times 1 + max |z|:
+# the residuals bound the objective, not z (DESIGN.md 3.22); 1e-8 keeps z of farmer (up to 250 per crop)
+# within 2.5e-6, a quarter of the project's 1e-5 on W and x̄
+DEFAULT_BUNDLE_STEP_TOL = 1e-8
+DEFAULT_BUNDLE_MAX_ITER = 100
 
 
 # phgpu_options structs by their settings (built once: the PH loop solves with the same
@@ -91,6 +114,9 @@ class SPOpt(SPBase):
         self.spcomm = None
         self.engine = None
         self._fixed = False
+        self._bundles = None
+        if self.bundling:
+            self.subproblem_creation()
         self.solve_times = []
         self.pdhg_iters = []
 
@@ -108,6 +134,93 @@ class SPOpt(SPBase):
             if self.options.get("ipm_tuning"):
                 # a model's interior-point constants (e.g. examples/aircond.py IPM_TUNING)
                 self.engine.set_ipm_tuning(self.options["ipm_tuning"])
+            if self.bundling:
+                self._bundle_setup()
+
+    # spopt.py:805-836
+    def subproblem_creation(self, verbose=False):
+        """``local_subproblems`` keyed ``rank{r}bundle{b}``: this rank's bundles, each a contiguous
+        slice of the local scenarios."""
+        if self.multistage or self.batch.depth != 1:
+            raise RuntimeError(f"bundles serve two-stage problems only ({len(self.all_nodenames)} tree nodes)")
+        if self.options.get("shared_matrix"):
+            raise NotImplementedError("bundles: a shared-matrix handle has no per-scenario matrix to factor")
+        self.bundle_tol = float(self.options.get("bundle_tol", DEFAULT_BUNDLE_TOL))
+        self.bundle_step_tol = float(self.options.get("bundle_step_tol", DEFAULT_BUNDLE_STEP_TOL))
+        self.bundle_max_iter = int(self.options.get("bundle_max_iter", DEFAULT_BUNDLE_MAX_ITER))
+        if not self.bundle_tol > 0.0 or not self.bundle_step_tol > 0.0 or self.bundle_max_iter < 0:
+            raise ValueError(f"bundle_tol = {self.bundle_tol} and bundle_step_tol = {self.bundle_step_tol} must be positive "
+                             f"and bundle_max_iter = {self.bundle_max_iter} non-negative")
+        r = self.cylinder_rank
+        self._bundles, first = {}, 0
+        for b, names in self.names_in_bundles[r].items():
+            if names != self.local_scenario_names[first:first + len(names)]:
+                raise RuntimeError(f"bundle {b} of rank {r} is not a contiguous slice of the rank's scenarios")
+            last = first + len(names)
+            self._bundles[f"rank{r}bundle{b}"] = Bundle(self, f"rank{r}bundle{b}", names, first, last,
+                                                        self.batch.prob[first:last].sum())
+            first = last
+        self.bundle_ipm_iters = []     # per solve_loop: (max, mean) interior-point iterations over the bundles
+
+    def _bundle_data(self):
+        """What phgpu_bundle_init takes, after the checks of what the segmented interior point does
+        not serve (those of opt/sc.py, per bundle)."""
+        from .opt.lshaped import first_stage_rows
+        b = self.batch
+        if b.nn > 64 or b.m > 64:
+            raise NotImplementedError(f"bundles: the interior point serves nn <= 64 and m <= 64 (nn {b.nn}, m {b.m})")
+        rows, _, lo, hi, _ = first_stage_rows(b)
+        for i, l, u in zip(rows, lo, hi):
+            if l == u:
+                raise NotImplementedError(f"bundles: row {i} has only nonant columns and equal sides [{l}, {u}]: its block of "
+                                          f"the scenario's normal matrix has no interior")
+        nc = np.asarray(b.nonant_col, dtype=np.int64)
+        oth = np.setdiff1d(np.arange(b.n), nc)
+        ranged = b.rl < b.ru
+        G = len(self._bundles)
+        seg = np.zeros(G + 1, dtype=np.int32)
+        zlb, zub, ncomp, cmax = np.zeros((G, b.nn)), np.zeros((G, b.nn)), np.zeros(G), np.zeros(G)
+        for g, (name, bd) in enumerate(self._bundles.items()):
+            sl = slice(bd.first, bd.last)
+            seg[g + 1] = bd.last
+            zlb[g], zub[g] = b.lb[sl][:, nc].max(axis=0), b.ub[sl][:, nc].min(axis=0)
+            if not np.all(zlb[g] < zub[g]):
+                k = int(np.nonzero(~(zlb[g] < zub[g]))[0][0])
+                raise NotImplementedError(f"bundle {name}: nonant {k} has the bounds [{zlb[g, k]}, {zub[g, k]}] over its "
+                                          f"scenarios: a fixed first-stage column leaves the interior point no interior")
+            ncomp[g] = (np.isfinite(b.lb[sl][:, oth]).sum() + np.isfinite(b.ub[sl][:, oth]).sum()
+                        + (np.isfinite(b.rl[sl]) & ranged[sl]).sum() + (np.isfinite(b.ru[sl]) & ranged[sl]).sum()
+                        + np.isfinite(zlb[g]).sum() + np.isfinite(zub[g]).sum())
+            cmax[g] = np.abs(b.c[sl]).max(initial=0.0)
+        return seg, zlb, zub, ncomp, cmax, bool(np.any(b.q))
+
+    def _bundle_setup(self):
+        e = self.engine
+        if e.shared:
+            raise NotImplementedError("bundles: a shared-matrix handle has no per-scenario matrix to factor")
+        data = self._bundle_data()
+        e.bundle_init(*data[:5], self.bundle_tol, self.bundle_step_tol, data[5])
+
+    def _bundle_solve(self, dtiming):
+        """Every bundle's extensive form at once (engine.bundle_solve), under the engine's W_on /
+        prox_on: Iter0's LPs, the PH QPs and the Lagrangian pass alike."""
+        r = self.engine.bundle_solve(self.bundle_max_iter)
+        self.bundle_last = r
+        if dtiming or self.options.get("record_pdhg_iters", False):
+            it = self.engine.iters.cpu().numpy()[[bd.first for bd in self._bundles.values()]]
+            self.pdhg_iters.append((int(it.max()), float(it.mean())))
+            self.bundle_ipm_iters.append(self.pdhg_iters[-1])
+        if r["open"] > 0 or r["stopped"] > 0:
+            self._bundle_gripe()
+
+    def _bundle_gripe(self):
+        st, it = self.engine.host("status"), self.engine.host("iters")
+        for name, bd in self._bundles.items():
+            if st[bd.first] != _lib.OPTIMAL:
+                self.bundle_griped = getattr(self, "bundle_griped", 0) + 1     # bundle solves griped so far
+                print(f"Solve of bundle {name} ended without optimality after {int(it[bd.first])} interior-point "
+                      f"iterations (status {int(st[bd.first])}, bundle_tol {self.bundle_tol:g}, bundle_max_iter "
+                      f"{self.bundle_max_iter}); its nonants are the last finite iterate's", flush=True)
 
     # options the reference's cfg_vanilla.shared_options passes to MIP/LP plugins
     # (threads, mipgap; cfg_vanilla.py:41-62) or that only drive plugin output (Tee):
@@ -135,8 +248,15 @@ class SPOpt(SPBase):
             for sp in self._subproblems():
                 ext.pre_solve(sp)
         t0 = time.perf_counter()
-        self.engine.solve(self._to_phgpu_options(solver_options), warm=warm_start, speculative=speculative)
-        if dtiming or self.options.get("record_pdhg_iters", False):
+        if self.bundling:
+            if speculative:
+                raise NotImplementedError("the speculative solve is not served with bundles: a bundle solve reads the "
+                                          "host's record every interior-point iteration")
+            self._bundle_solve(dtiming)
+            gripe = False            # (_bundle_solve gripes by bundle name)
+        else:
+            self.engine.solve(self._to_phgpu_options(solver_options), warm=warm_start, speculative=speculative)
+        if not self.bundling and (dtiming or self.options.get("record_pdhg_iters", False)):
             import torch
             torch.cuda.synchronize()
             it = self.engine.iters.cpu().numpy()
@@ -159,6 +279,8 @@ class SPOpt(SPBase):
 
     def _subproblems(self):
         """Per-scenario models when the creator built them, else ScenarioViews."""
+        if self.bundling:
+            return list(self._bundles.values())
         if self.local_scenarios:
             return [self.local_scenarios[nm] for nm in self.local_scenario_names]
         return [ScenarioView(self, k, nm) for k, nm in enumerate(self.local_scenario_names)]
@@ -171,6 +293,14 @@ class SPOpt(SPBase):
         # spopt.py:165-221: the results object with termination 'infeasible' / 'unbounded'
         # (and no solution) for a certified failure; None only where the solver raised,
         # which a batched launch does not do per scenario
+        if self.bundling:
+            # a bundle's objective is sum_s (p_s / p_B) of its scenarios'; status and iterations are the bundle's
+            p = self.batch.prob
+            for sp in self._subproblems():
+                sl, k = slice(sp.first, sp.last), sp.first
+                w = p[sl] / sp._mpisppy_probability
+                ext.post_solve(sp, ScenarioResults(st[k], sense * float(w @ obj[sl]), sense * float(w @ bd[sl]), it[k], sense))
+            return
         for k, sp in enumerate(self._subproblems()):
             ext.post_solve(sp, ScenarioResults(st[k], sense * obj[k], sense * bd[k], it[k], sense))
 
@@ -237,6 +367,11 @@ class SPOpt(SPBase):
         """Fix the nonants of all local scenarios: ``cache`` is {node name: values} or a
         device [num_nodes, nlen_max] tensor (global node order)."""
         import torch
+        if self.bundling:
+            # (a bundle solve reads the problem's own bounds and z's, set once: fixed nonants would be
+            # ignored and the free bundle's objective reported as the value at the candidate)
+            raise NotImplementedError("fixing the nonants (_fix_nonants: the xhat extensions and spokes, Xhat_Eval) is not "
+                                      "served with bundles: a fixed column leaves a bundle's interior point no interior")
         tab = cache if torch.is_tensor(cache) else self._node_table(cache)
         self.engine.fix_nonants_by_node(tab)
         self._fixed = True

@@ -901,6 +901,50 @@ int phgpu_bundle_step(phgpu_handle h, int32_t stage, void* stream);
 int phgpu_bundle_export(phgpu_handle h, double* x, double* y, double* obj, double* bound, int32_t* status,
                         int32_t* iters, void* stream);
 
+/* The extensive form of a MULTISTAGE problem (mpisppy/opt/ef.py:39-64 with all_nodenames;
+ * sputils.create_EF ties the nonants of every non-leaf node): the interior point of phgpu_ef_* with
+ * x_s[N_d] = z_{node of s at depth d} for every depth d < D, one mu, one pair of step lengths, one
+ * test.  z is the concatenation over the non-leaf nodes, in node order, of
+ * nlens[depth] values each (Ztot in all).  The Schur complement in dz is block-sparse with the shape
+ * of the tree and is eliminated bottom-up, a wave per node; ROOT's block is solved as phgpu_ef_*
+ * solves C.  One rank; all entries are ordered on the stream, none synchronises, no floating-point
+ * atomics: the same input gives the same bits.  An iteration is, per right-hand side,
+ * phgpu_eft_schur -> phgpu_eft_direction -> phgpu_eft_step.
+ *
+ * phgpu_eft_init: allocate the store (the handle's; freed by phgpu_destroy or another init) and set
+ * the start.  HOST arrays: nlens [D] the nonants per depth (their sum is the handle's nn, whose
+ * nonant slots are ordered by depth); node_depth, node_parent [Nn] the non-leaf nodes numbered depth
+ * by depth, node 0 ROOT (parent -1), the children of a node adjacent and in their parents' order;
+ * seg_start [G + 1] the contiguous scenario range of each node of depth D - 1, in node order (0 =
+ * seg_start[0] < ... < seg_start[G] = S); zlb < zub, cz, qz >= 0 [Ztot] per z entry the tightest
+ * bounds and the probability-weighted cost and diagonal over the node's scenarios; ncomp, cmax, tol,
+ * qp as phgpu_ef_init.  -3: a shared-matrix handle; -1: D < 2 or not the handle's depth, nn or m >
+ * 64, a tree out of that order, an entry of z without an interior. */
+int phgpu_eft_init(phgpu_handle h, int32_t D, const int32_t* nlens, int32_t Nn, const int32_t* node_depth,
+                   const int32_t* node_parent, const int32_t* seg_start, const double* zlb, const double* zub,
+                   const double* cz, const double* qz, double ncomp, double cmax, double tol, int32_t qp, void* stream);
+
+/* The scenario pass (phgpu_ef_schur's, on the scenario's whole path), the segmented sums of its
+ * terms per deepest node (a thread or, for long segments, a block per value and segment; index
+ * order), the elimination of depth D - 1 .. 1 and ROOT's sums.  Optional device copies for
+ * inspection (NULL: none): nodeA [Nn][nn * nn] the lower triangle of every node's P_d x P_d matrix
+ * as summed from its scenarios or children, before its own Dz^-1 (stage 0), nodeb [Nn][nn] its
+ * right-hand side likewise (rows and columns in path order). */
+int phgpu_eft_schur(phgpu_handle h, int32_t stage, double* nodeA, double* nodeb, void* stream);
+
+/* ROOT's test (stage 0), factor and solve as phgpu_ef_direction's, the back-substitution depth 1 ..
+ * D - 1, the direction pass and its sums and maxima over the scenarios and the nodes.
+ *   info: phgpu_ef_direction's double[8], device or host-mapped pinned memory. */
+int phgpu_eft_direction(phgpu_handle h, int32_t stage, double* info, void* stream);
+
+/* phgpu_ef_step over the scenarios and every node's z entries. */
+int phgpu_eft_step(phgpu_handle h, int32_t stage, void* stream);
+
+/* phgpu_ef_export: every scenario's nonant columns hold its path's z (bitwise equal between the
+ * scenarios that share the node).  z [Ztot] device, may be NULL. */
+int phgpu_eft_export(phgpu_handle h, double* x, double* y, double* obj, double* bound, int32_t* status,
+                     int32_t* iters, double* z, void* stream);
+
 /* Free the workspace and the handle. */
 int phgpu_destroy(phgpu_handle h);
 

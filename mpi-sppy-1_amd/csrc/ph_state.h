@@ -21,6 +21,7 @@ struct sel_state;   // ph_aph.inc: the workspace of phgpu_select_smallest
 struct ls_store;    // ph_lshaped.inc: the cut store and master of the L-shaped method
 struct ef_store;    // ph_ef.inc: the iterate and work space of the extensive-form interior point
 struct bd_store;    // phgpu.hip: the segmented form of it, one extensive form per bundle
+struct eft_store;   // phgpu.hip: the multistage form of it, eliminated along the tree (ph_ef_tree.inc)
 struct ph_ws {      // a reduction's device workspace: partials, and node tags or a ticket counter
     double* part;
     int32_t* tag;
@@ -252,6 +253,9 @@ struct phgpu_state : pdhg_view {
     // phgpu_bundle_*: the segmented extensive-form interior point (one segment per bundle; host
     // record of its device buffers; null until phgpu_bundle_init)
     bd_store* bd;
+    // phgpu_eft_*: the multistage extensive-form interior point (host record of its device buffers;
+    // null until phgpu_eft_init)
+    eft_store* eft;
     // phgpu_gap_moments: two slots of GM_NV partials per wave (its head and its tail run) and
     // their segment tags [2 * nwaves], allocated at its first call
     ph_ws gm;

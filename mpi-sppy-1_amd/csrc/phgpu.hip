@@ -845,6 +845,7 @@ __global__ void k_stats_copy(const unsigned long long* __restrict__ src, int cop
 #include "ph_aph.inc"
 #include "ph_lshaped.inc"
 #include "ph_ef.inc"
+#include "ph_ef_tree.inc"
 #include "ph_gap.inc"
 
 // Xhat_Eval._fix_nonants (utils/xhat_eval.py; spopt.py _fix_nonants): nonant columns of
@@ -3557,6 +3558,293 @@ extern "C" int phgpu_bundle_export(phgpu_handle h, double* x, double* y, double*
     return 0;
 }
 
+// ------------------------------------------------------------------ the multistage extensive form (ph_ef_tree.inc)
+// One interior point over a scenario tree (mpisppy/opt/ef.py with all_nodenames, sputils.create_EF),
+// its Schur complement eliminated along the tree.
+struct eft_store {
+    ef_store E;  // zd: G copies (one per deepest non-leaf node), C: ROOT's factor, ctl: one record
+    eft_tree T;
+    int32_t *depth, *child0, *nchild, *zoff, *path, *P, *seg_start, *seg_of;
+    int block_reduce;            // the segmented sum by a block per (plane, segment)
+    std::vector<int> lvl0;       // [D + 1]: the first node of each depth
+    std::vector<int> Ph;         // [D]: P_d on the host
+};
+
+static void eft_release(phgpu_state* h) {
+    eft_store* X = h->eft;
+    if (!X) return;
+    ef_store* E = &X->E;
+    dfree(h, &E->x); dfree(h, &E->zl); dfree(h, &E->zu); dfree(h, &E->dx); dfree(h, &E->dxa); dfree(h, &E->D);
+    dfree(h, &E->w); dfree(h, &E->vl); dfree(h, &E->vu); dfree(h, &E->y); dfree(h, &E->dw); dfree(h, &E->dwa);
+    dfree(h, &E->dy); dfree(h, &E->dya); dfree(h, &E->g); dfree(h, &E->wk); dfree(h, &E->rp); dfree(h, &E->E);
+    dfree(h, &E->fac); dfree(h, &E->terms); dfree(h, &E->zd); dfree(h, &E->C); dfree(h, &E->ctl);
+    eft_tree* T = &X->T;
+    dfree(h, &T->zn); dfree(h, &T->rootzd); dfree(h, &T->slot); dfree(h, &T->hv); dfree(h, &T->ty); dfree(h, &T->nsc);
+    dfree(h, &T->segsum); dfree(h, &T->segmax); dfree(h, &T->rootsum); dfree(h, &T->rootmax); dfree(h, &T->lsum);
+    dfree(h, &T->lmax); dfree(h, &T->dirsum); dfree(h, &T->dirmax);
+    dfree(h, &X->depth); dfree(h, &X->child0); dfree(h, &X->nchild); dfree(h, &X->zoff); dfree(h, &X->path); dfree(h, &X->P);
+    dfree(h, &X->seg_start); dfree(h, &X->seg_of);
+    delete X;
+    h->eft = nullptr;
+}
+
+// a segment at least this long on average is summed by a block per (plane, segment)
+#define EFT_BLOCK_REDUCE_LEN GR_T
+
+extern "C" int phgpu_eft_init(phgpu_handle h, int32_t D, const int32_t* nlens, int32_t Nn, const int32_t* node_depth,
+                              const int32_t* node_parent, const int32_t* seg_start, const double* zlb, const double* zub,
+                              const double* cz, const double* qz, double ncomp, double cmax, double tol, int32_t qp,
+                              void* stream) {
+    if (!h) return set_err(-1, "null handle");
+    if (!h->scen_set) return set_err(-1, "phgpu_eft_init: no scenario data yet");
+    if (h->shared) return set_err(-3, "phgpu_eft_init: a shared-matrix handle is not served");
+    if (!nlens || !node_depth || !node_parent || !seg_start || !zlb || !zub || !cz || !qz) return set_err(-1, "null argument");
+    if (D < 2 || D != h->depth) return set_err(-1, "phgpu_eft_init: depth %d (the handle's %d; at least 2)", (int)D, h->depth);
+    if (h->nn < 1 || h->nn > EF_NN_MAX || h->m < 1 || h->m > EF_M_MAX)
+        return set_err(-1, "phgpu_eft_init: nn %d (1..%d), m %d (1..%d)", h->nn, EF_NN_MAX, h->m, EF_M_MAX);
+    if (!(ncomp >= 1.0) || !(cmax >= 0.0) || !(tol > 0.0))
+        return set_err(-1, "phgpu_eft_init: ncomp %g, cmax %g, tol %g", ncomp, cmax, tol);
+    const int nn = h->nn, m = h->m, n = h->n;
+    std::vector<int32_t> P(D);
+    for (int d = 0, a = 0; d < D; ++d) {
+        if (nlens[d] < 1) return set_err(-1, "phgpu_eft_init: depth %d has %d nonants", d, (int)nlens[d]);
+        P[d] = (a += nlens[d]);
+    }
+    if (P[D - 1] != nn) return set_err(-1, "phgpu_eft_init: nlens sum to %d, the handle's nn is %d", (int)P[D - 1], nn);
+    // the nodes: depth by depth, ROOT first, children of one node adjacent and in their parents' order
+    if (Nn < D || node_depth[0] != 0 || node_parent[0] != -1) return set_err(-1, "phgpu_eft_init: node 0 is not ROOT");
+    std::vector<int32_t> child0(Nn, 0), nchild(Nn, 0), zoff(Nn, 0), path((size_t)Nn * nn, 0);
+    std::vector<int> lvl0(D + 1, Nn);
+    lvl0[0] = 0;
+    int Ztot = P[0];
+    for (int k = 0; k < P[0]; ++k) path[k] = k;
+    for (int i = 1; i < Nn; ++i) {
+        const int d = node_depth[i], p = node_parent[i];
+        if (d < 1 || d >= D || d < node_depth[i - 1] || d > node_depth[i - 1] + 1 || p < 0 || p >= i || node_depth[p] != d - 1 ||
+            (node_depth[i - 1] == d && p < node_parent[i - 1]))
+            return set_err(-1, "phgpu_eft_init: node %d (depth %d, parent %d) is out of the depth-by-depth order", i, d, p);
+        if (node_depth[i - 1] != d) lvl0[d] = i;
+        if (nchild[p] == 0) child0[p] = i;
+        else if (child0[p] + nchild[p] != i) return set_err(-1, "phgpu_eft_init: the children of node %d are not adjacent", p);
+        ++nchild[p];
+        zoff[i] = Ztot;
+        for (int k = 0; k < P[d - 1]; ++k) path[(size_t)i * nn + k] = path[(size_t)p * nn + k];
+        for (int k = P[d - 1]; k < P[d]; ++k) path[(size_t)i * nn + k] = Ztot + (k - P[d - 1]);
+        Ztot += nlens[d];
+    }
+    if (node_depth[Nn - 1] != D - 1) return set_err(-1, "phgpu_eft_init: no node of depth %d", (int)D - 1);
+    const int deep0 = lvl0[D - 1], G = Nn - deep0;
+    for (int i = 0; i < deep0; ++i)
+        if (nchild[i] == 0) return set_err(-1, "phgpu_eft_init: node %d of depth %d has no child", i, (int)node_depth[i]);
+    if (seg_start[0] != 0 || (int64_t)seg_start[G] != h->S)
+        return set_err(-1, "phgpu_eft_init: the %d segments span [%d, %d), not the %lld local scenarios", G, (int)seg_start[0],
+                       (int)seg_start[G], (long long)h->S);
+    for (int g = 0; g < G; ++g)
+        if (seg_start[g + 1] <= seg_start[g]) return set_err(-1, "phgpu_eft_init: segment %d is empty", g);
+    for (int k = 0; k < Ztot; ++k)
+        if (!(zlb[k] < zub[k]) || zlb[k] == INFINITY || zub[k] == -INFINITY || !(qz[k] >= 0.0))
+            return set_err(-1, "phgpu_eft_init: z entry %d has bounds [%g, %g] (no interior) or q %g", k, zlb[k], zub[k], qz[k]);
+    FLUSH_STEP(h);
+    hipStream_t st = (hipStream_t)stream;
+    if (h->eft) {
+        HIPCHK(hipStreamSynchronize(st));  // (nothing of the old store may be in flight)
+        eft_release(h);
+    }
+    eft_store* X = new (std::nothrow) eft_store();
+    if (!X) return set_err(-3, "out of host memory");
+    h->eft = X;
+    ef_store* E = &X->E;
+    eft_tree* T = &X->T;
+    memset(E, 0, sizeof(*E));
+    memset(T, 0, sizeof(*T));
+    X->lvl0 = lvl0;
+    X->Ph.assign(P.begin(), P.end());
+    E->nn = nn; E->m = m; E->n = n; E->ntri = nn * (nn + 1) / 2; E->ld = nn | 1;
+    E->nplanes = ef_nsum0(*E) + 2;
+    T->D = D; T->Nn = Nn; T->G = G; T->nn = nn; T->ld = nn | 1; T->Ztot = Ztot; T->P0 = P[0]; T->deep0 = deep0;
+    T->nsum0 = ef_nsum0(*E);
+    const size_t S = (size_t)h->S;
+    X->block_reduce = S / (size_t)G >= (size_t)EFT_BLOCK_REDUCE_LEN;
+    const int P0 = P[0], nsumR = P0 * (P0 + 1) / 2 + 2 * P0 + 2;
+    int rc = 0;
+    for (double** p : {&E->x, &E->zl, &E->zu, &E->dx, &E->dxa, &E->D})
+        if (!rc) rc = dalloc(h, p, (size_t)n * S);
+    for (double** p : {&E->w, &E->vl, &E->vu, &E->y, &E->dw, &E->dwa, &E->dy, &E->dya, &E->g, &E->wk, &E->rp, &E->E})
+        if (!rc) rc = dalloc(h, p, (size_t)m * S);
+    if (!rc) rc = dalloc(h, &E->fac, (size_t)(m * (m + 1) / 2) * S);
+    if (!rc) rc = dalloc(h, &E->terms, (size_t)E->nplanes * S);
+    if (!rc) rc = dalloc(h, &E->C, (size_t)P0 * (P0 | 1));
+    if (!rc) rc = dalloc(h, &E->zd, (size_t)G * EF_ZD_LEN(*E));
+    if (!rc) rc = dalloc(h, &T->slot, (size_t)Nn * nn * T->ld);
+    if (!rc) rc = dalloc(h, &T->hv, (size_t)Nn * nn);
+    if (!rc) rc = dalloc(h, &T->ty, (size_t)Nn * nn);
+    if (!rc) rc = dalloc(h, &T->nsc, (size_t)Nn * 2);
+    if (!rc) rc = dalloc(h, &T->segsum, (size_t)G * T->nsum0);
+    if (!rc) rc = dalloc(h, &T->segmax, (size_t)G * 2);
+    if (!rc) rc = dalloc(h, &T->rootsum, (size_t)nsumR);
+    if (!rc) rc = dalloc(h, &T->rootmax, (size_t)2);
+    if (!rc) rc = dalloc(h, &T->lsum, (size_t)3);
+    if (!rc) rc = dalloc(h, &T->lmax, (size_t)2);
+    if (!rc) rc = dalloc(h, &T->dirsum, (size_t)3);
+    if (!rc) rc = dalloc(h, &T->dirmax, (size_t)2);
+    // z's start, as phgpu_ef_init sets it: ROOT's fields in its own block, the other nodes' by z index
+    std::vector<double> zn((size_t)(EZ_N + 1) * Ztot, 0.0), rz((size_t)(EZ_N + 1) * P0, 0.0), ctl(EF_CTL, 0.0);
+    for (int k = 0; k < Ztot; ++k) {
+        double* base = k < P0 ? rz.data() + k : zn.data() + k;
+        const size_t ldz = k < P0 ? (size_t)P0 : (size_t)Ztot;
+        base[EZ_LB * ldz] = zlb[k]; base[EZ_UB * ldz] = zub[k]; base[EZ_C * ldz] = cz[k]; base[EZ_Q * ldz] = qz[k];
+        base[EZ_Z * ldz] = ef_inside(zlb[k], zub[k]);
+        base[EZ_ZL * ldz] = isfinite(zlb[k]) ? 1.0 + fabs(cz[k]) : 0.0;
+        base[EZ_ZU * ldz] = isfinite(zub[k]) ? 1.0 + fabs(cz[k]) : 0.0;
+    }
+    ctl[EC_NCOMP] = ncomp; ctl[EC_CMAX] = cmax; ctl[EC_TOL] = tol; ctl[EC_QP] = qp ? 1.0 : 0.0;
+    std::vector<int32_t> seg_of(S), depth(node_depth, node_depth + Nn);
+    for (int g = 0; g < G; ++g)
+        for (int32_t s = seg_start[g]; s < seg_start[g + 1]; ++s) seg_of[s] = g;
+    if (!rc) rc = ls_upload(h, &T->zn, zn.data(), zn.size());
+    if (!rc) rc = ls_upload(h, &T->rootzd, rz.data(), rz.size());
+    if (!rc) rc = ls_upload(h, &E->ctl, ctl.data(), ctl.size());
+    if (!rc) rc = ls_upload(h, &X->depth, depth.data(), depth.size());
+    if (!rc) rc = ls_upload(h, &X->child0, child0.data(), child0.size());
+    if (!rc) rc = ls_upload(h, &X->nchild, nchild.data(), nchild.size());
+    if (!rc) rc = ls_upload(h, &X->zoff, zoff.data(), zoff.size());
+    if (!rc) rc = ls_upload(h, &X->path, path.data(), path.size());
+    if (!rc) rc = ls_upload(h, &X->P, P.data(), P.size());
+    if (!rc) rc = ls_upload(h, &X->seg_start, seg_start, (size_t)G + 1);
+    if (!rc) rc = ls_upload(h, &X->seg_of, seg_of.data(), seg_of.size());
+    if (rc) {
+        eft_release(h);
+        return rc;
+    }
+    T->depth = X->depth; T->child0 = X->child0; T->nchild = X->nchild; T->zoff = X->zoff; T->path = X->path; T->P = X->P;
+    T->seg_start = X->seg_start; T->seg_of = X->seg_of;
+#define EFT_CHK(call)                                                                                         \
+    do {                                                                                                      \
+        hipError_t e_ = (call);                                                                               \
+        if (e_ != hipSuccess) {                                                                               \
+            eft_release(h);                                                                                   \
+            return set_err(-2, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__);  \
+        }                                                                                                     \
+    } while (0)
+    EFT_CHK(hipMemsetAsync(E->terms, 0, (size_t)E->nplanes * S * sizeof(double), st));
+    EFT_CHK(hipMemsetAsync(E->zd, 0, (size_t)G * EF_ZD_LEN(*E) * sizeof(double), st));
+    EFT_CHK(hipMemsetAsync(T->slot, 0, (size_t)Nn * nn * T->ld * sizeof(double), st));
+    EFT_CHK(hipMemsetAsync(T->hv, 0, (size_t)Nn * nn * sizeof(double), st));
+    EFT_CHK(hipMemsetAsync(T->ty, 0, (size_t)Nn * nn * sizeof(double), st));
+    EFT_CHK(hipMemsetAsync(T->nsc, 0, (size_t)Nn * 2 * sizeof(double), st));
+    EFT_CHK(hipMemsetAsync(T->segsum, 0, (size_t)G * T->nsum0 * sizeof(double), st));
+    EFT_CHK(hipMemsetAsync(T->segmax, 0, (size_t)G * 2 * sizeof(double), st));
+    EFT_CHK(hipMemsetAsync(T->rootsum, 0, (size_t)nsumR * sizeof(double), st));
+    EFT_CHK(hipMemsetAsync(T->rootmax, 0, 2 * sizeof(double), st));
+#undef EFT_CHK
+    hipLaunchKernelGGL(k_ef_start, dim3((unsigned)((h->S + EF_T - 1) / EF_T)), dim3(EF_T), 0, st, *h, *E);
+    hipLaunchKernelGGL(k_eft_gather, dim3((unsigned)((G * nn + EF_T - 1) / EF_T)), dim3(EF_T), 0, st, *E, *T, (int)EZ_Z);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+#define EFT_READY(h, who, stage)                                                             \
+    do {                                                                                     \
+        if (!(h)) return set_err(-1, "null handle");                                         \
+        if (!(h)->eft) return set_err(-1, who ": phgpu_eft_init has not run");               \
+        if ((stage) != 0 && (stage) != 1) return set_err(-1, who ": stage %d", (int)(stage)); \
+        FLUSH_STEP(h);                                                                       \
+    } while (0)
+#define EFT_GATHER(X, f, st) \
+    hipLaunchKernelGGL(k_eft_gather, dim3((unsigned)(((X).T.G * (X).T.nn + EF_T - 1) / EF_T)), dim3(EF_T), 0, st, (X).E, (X).T, (int)(f))
+
+// the scenario pass, its segmented sums, the elimination up the tree and ROOT's sums
+extern "C" int phgpu_eft_schur(phgpu_handle h, int32_t stage, double* nodeA, double* nodeb, void* stream) {
+    EFT_READY(h, "phgpu_eft_schur", stage);
+    hipStream_t st = (hipStream_t)stream;
+    const eft_store& X = *h->eft;
+    const ef_store& E = X.E;
+    eft_tree T = X.T;
+    T.inspA = stage == 0 ? nodeA : nullptr;
+    T.inspb = nodeb;
+    hipLaunchKernelGGL(k_eft_schur, BD_GRID(h), dim3(EF_T), 0, st, *h, E, T, (int)stage);
+    const int nsum = stage == 0 ? T.nsum0 : T.nn, nmax = stage == 0 ? 2 : 0;
+    if (X.block_reduce) {
+        hipLaunchKernelGGL(k_eft_reduce_b, dim3((unsigned)(nsum + nmax), (unsigned)T.G), dim3(GR_T), 0, st, E, T, h->S, nsum);
+    } else {
+        const int64_t nt = (int64_t)(nsum + nmax) * T.G;
+        hipLaunchKernelGGL(k_eft_reduce_t, dim3((unsigned)((nt + GR_T - 1) / GR_T)), dim3(GR_T), 0, st, E, T, h->S, nsum, nmax);
+    }
+    for (int d = T.D - 1; d >= 1; --d) {
+        const int n0 = X.lvl0[d], cnt = X.lvl0[d + 1] - n0;
+        const int Pd = X.Ph[d];  // (the workspace of this depth: P_d rows of the odd leading dimension, b and T'y)
+        const size_t lds = ((size_t)Pd * T.ld + 2 * (size_t)Pd) * sizeof(double);
+        hipLaunchKernelGGL(k_eft_elim, dim3((unsigned)cnt), dim3(WAVE), lds, st, E, T, n0, (int)stage);
+    }
+    hipLaunchKernelGGL(k_eft_root, dim3(1), dim3(GR_T), 0, st, E, T, (int)stage);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ROOT's solve (ef_solve_core on its view), the back-substitution down the tree, the direction
+// pass and its sums and maxima with the nodes' share
+extern "C" int phgpu_eft_direction(phgpu_handle h, int32_t stage, double* info, void* stream) {
+    EFT_READY(h, "phgpu_eft_direction", stage);
+    if (!info) return set_err(-1, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    const eft_store& X = *h->eft;
+    const ef_store& E = X.E;
+    const eft_tree& T = X.T;
+    const ef_store R = eft_root_view(E, T);
+    const size_t lds = ((size_t)R.nn * R.ld + R.nn) * sizeof(double);
+    hipLaunchKernelGGL(k_ef_solve, dim3(1), dim3(LS_T), lds, st, R, (int)stage, (const double*)T.rootsum,
+                       (const double*)T.rootmax, info);
+    for (int d = 1; d < T.D; ++d) {
+        const int n0 = X.lvl0[d], cnt = X.lvl0[d + 1] - n0;
+        hipLaunchKernelGGL(k_eft_back, dim3((unsigned)((cnt + EF_T - 1) / EF_T)), dim3(EF_T), 0, st, E, T, n0, cnt);
+    }
+    EFT_GATHER(X, EZ_DZ, st);
+    hipLaunchKernelGGL(k_eft_direction, BD_GRID(h), dim3(EF_T), 0, st, *h, E, T, (int)stage);
+    hipLaunchKernelGGL(k_ef_reduce, dim3(5), dim3(GR_T), 0, st, E, h->S, 3, T.lsum, T.lmax);
+    hipLaunchKernelGGL(k_eft_dirsum, dim3(1), dim3(GR_T), 0, st, E, T, (int)stage);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// the step lengths and sigma (stage 0), the step (stage 1): ef_ctrl_core on ROOT's view, then the
+// other nodes' z entries and the lanes
+extern "C" int phgpu_eft_step(phgpu_handle h, int32_t stage, void* stream) {
+    EFT_READY(h, "phgpu_eft_step", stage);
+    hipStream_t st = (hipStream_t)stream;
+    const eft_store& X = *h->eft;
+    const ef_store& E = X.E;
+    const eft_tree& T = X.T;
+    hipLaunchKernelGGL(k_ef_ctrl, dim3(1), dim3(WAVE), 0, st, eft_root_view(E, T), (int)stage, (const double*)T.dirsum,
+                       (const double*)T.dirmax);
+    hipLaunchKernelGGL(k_eft_zstep, dim3((unsigned)((T.Ztot - T.P0 + EF_T - 1) / EF_T)), dim3(EF_T), 0, st, E, T, (int)stage);
+    if (stage == 0) {
+        hipLaunchKernelGGL(k_ef_keep, BD_GRID(h), dim3(EF_T), 0, st, *h, E);
+    } else {
+        hipLaunchKernelGGL(k_ef_step, BD_GRID(h), dim3(EF_T), 0, st, *h, E);
+        EFT_GATHER(X, EZ_Z, st);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int phgpu_eft_export(phgpu_handle h, double* x, double* y, double* obj, double* bound, int32_t* status,
+                                int32_t* iters, double* z, void* stream) {
+    EFT_READY(h, "phgpu_eft_export", 0);
+    if (!x || !obj || !bound || !status || !iters) return set_err(-1, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    const eft_store& X = *h->eft;
+    const eft_tree& T = X.T;
+    hipLaunchKernelGGL(k_eft_export, BD_GRID(h), dim3(EF_T), 0, st, *h, X.E, T, x, y, obj, bound, status, iters);
+    HIPCHK(hipGetLastError());
+    if (z) {
+        HIPCHK(hipMemcpyAsync(z, T.rootzd + (size_t)EZ_Z * T.P0, (size_t)T.P0 * sizeof(double), hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(z + T.P0, T.zn + (size_t)EZ_Z * T.Ztot + T.P0, (size_t)(T.Ztot - T.P0) * sizeof(double),
+                              hipMemcpyDeviceToDevice, st));
+    }
+    h->last_stats = nullptr;
+    return 0;
+}
+
 #include "comm_rccl.inc"
 
 extern "C" int phgpu_destroy(phgpu_handle h) {
@@ -3569,6 +3857,7 @@ extern "C" int phgpu_destroy(phgpu_handle h) {
     delete h->ls;
     delete h->ef;
     delete h->bd;
+    delete h->eft;
     phgpu_owner* o = owner_of(h);  // (a deferred step that never ran is dropped with it)
     for (const dev_alloc& a : o->allocs) (void)hipFree(a.p);
     delete o;

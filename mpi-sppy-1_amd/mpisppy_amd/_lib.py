@@ -91,7 +91,8 @@ EXPORTS = ["phgpu_default_options", "phgpu_create", "phgpu_create2", "phgpu_set_
            "phgpu_lshaped_load", "phgpu_lshaped_export", "phgpu_gap_moments",
            "phgpu_ef_init", "phgpu_ef_schur", "phgpu_ef_direction", "phgpu_ef_step", "phgpu_ef_export",
            "phgpu_bundle_init", "phgpu_bundle_start", "phgpu_bundle_schur", "phgpu_bundle_direction",
-           "phgpu_bundle_step", "phgpu_bundle_export"]
+           "phgpu_bundle_step", "phgpu_bundle_export",
+           "phgpu_eft_init", "phgpu_eft_schur", "phgpu_eft_direction", "phgpu_eft_step", "phgpu_eft_export"]
 
 _lib = None
 
@@ -179,6 +180,12 @@ def load(path=None):
     lib.phgpu_bundle_direction.argtypes = [c_vp, c_i32, c_vp, c_vp]
     lib.phgpu_bundle_step.argtypes = [c_vp, c_i32, c_vp]
     lib.phgpu_bundle_export.argtypes = [c_vp] + [c_vp] * 7
+    lib.phgpu_eft_init.argtypes = [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_dbl,
+                                   c_i32, c_vp]
+    lib.phgpu_eft_schur.argtypes = [c_vp, c_i32, c_vp, c_vp, c_vp]
+    lib.phgpu_eft_direction.argtypes = [c_vp, c_i32, c_vp, c_vp]
+    lib.phgpu_eft_step.argtypes = [c_vp, c_i32, c_vp]
+    lib.phgpu_eft_export.argtypes = [c_vp] + [c_vp] * 8
     lib.phgpu_gap_moments.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_vp]
     lib.phgpu_ipm_info.argtypes = [c_vp, ctypes.POINTER(c_dbl)]
     lib.phgpu_ipm_prof.argtypes = [c_vp, ctypes.POINTER(ctypes.c_ulonglong), c_i64]

@@ -298,10 +298,12 @@ def ef_xstar_solver(mname, solver_name=None, tol=1e-8, max_iter=100, device=None
     of each sample problem from ``ExtensiveForm`` (opt/ef.py: one interior point on the sample's
     extensive form, LPs and diagonal QPs, no cut groups and no master rounds) instead of the L-shaped method,
     which stays the default.  ``mname``: the model module or its name.  Returns the callable
-    (scenario_names, scenario_creator_kwargs) -> x* [nn]; a solve that does not reach ``tol``
+    (scenario_names, scenario_creator_kwargs) -> x* [ROOT's nonants] (on a multistage model, whose
+    kwargs hold ``branching_factors``, the extensive form is that of the whole tree); a solve that does not reach ``tol``
     within ``max_iter`` iterations raises."""
     from ..opt.ef import ExtensiveForm
     from ..spopt import SOLVER_NAMES
+    from ..sputils import create_nodenames_from_branching_factors
     m = model_module(mname) if isinstance(mname, str) else mname
 
     def solve(scenario_names, scenario_creator_kwargs):
@@ -309,7 +311,10 @@ def ef_xstar_solver(mname, solver_name=None, tol=1e-8, max_iter=100, device=None
                 "device": device}
         if hasattr(m, "batch_creator"):
             opts["batch_creator"] = m.batch_creator
-        ef = ExtensiveForm(opts, scenario_names, m.scenario_creator, scenario_creator_kwargs=scenario_creator_kwargs)
+        bfs = (scenario_creator_kwargs or {}).get("branching_factors")     # a multistage model names its tree by them
+        nodenames = create_nodenames_from_branching_factors(list(bfs)) if bfs is not None and len(bfs) > 1 else None
+        ef = ExtensiveForm(opts, scenario_names, m.scenario_creator, scenario_creator_kwargs=scenario_creator_kwargs,
+                           all_nodenames=nodenames)
         try:
             res = ef.solve_extensive_form()
             if res.solver.termination_condition != "optimal":

@@ -1577,6 +1577,76 @@ class PHEngine:
                                             _ptr(self.status), _ptr(self.iters), _ptr(self.ef_z), self._stream()),
                    "phgpu_ef_export")
 
+    # -------------------------------------------------------------- multistage extensive form
+    def eft_init(self, nlens, node_depth, node_parent, seg_start, zlb, zub, cz, qz, ncomp, cmax, tol, qp):
+        """The tree interior point's store and starting iterate (phgpu_eft_init): host
+        arrays nlens [D], node_depth, node_parent [Nn], seg_start [G + 1] and zlb, zub, cz, qz [Ztot]
+        in node order.  Buffers: ``ef_z`` [Ztot] and the pinned ``ef_info`` of ``ef_read``."""
+        self._flush_step()
+        i4 = lambda a: np.ascontiguousarray(a, dtype=np.int32)  # noqa: E731
+        nlens, node_depth, node_parent, seg_start = i4(nlens), i4(node_depth), i4(node_parent), i4(seg_start)
+        Ztot = int(nlens[node_depth].sum())
+        f8 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(Ztot))  # noqa: E731
+        zlb, zub, cz, qz = f8(zlb), f8(zub), f8(cz), f8(qz)
+        hp = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+        _lib.check(self.lib.phgpu_eft_init(self.h, len(nlens), hp(nlens), len(node_depth), hp(node_depth), hp(node_parent),
+                                           hp(seg_start), hp(zlb), hp(zub), hp(cz), hp(qz), float(ncomp), float(cmax),
+                                           float(tol), int(bool(qp)), self._stream()), "phgpu_eft_init")
+        self.eft_nodes, self.eft_ztot = len(node_depth), Ztot
+        self.ef_z = torch.zeros(Ztot, dtype=torch.float64, device=self.device)
+        self.ef_info = torch.zeros(8, dtype=torch.float64).pin_memory()
+        self._ef_info_np = self.ef_info.numpy()
+        self._ef_ev = torch.cuda.Event()
+        for k in ("eft_schur", "eft_direction", "eft_step"):
+            self.calls[k] = 0
+
+    def eft_schur(self, stage, inspect=False):
+        """The scenario pass, its sums per deepest node, the elimination up the tree and ROOT's sums
+        (phgpu_eft_schur).  Device work only.  ``inspect``: returns device copies (A [Nn, nn, nn]
+        lower triangles, b [Nn, nn]) of every node's matrix (stage 0) and right-hand side as summed."""
+        self.calls["eft_schur"] += 1
+        A = b = None
+        if inspect:
+            A = torch.zeros(self.eft_nodes, self.nn, self.nn, dtype=torch.float64, device=self.device)
+            b = torch.zeros(self.eft_nodes, self.nn, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.phgpu_eft_schur(self.h, int(stage), _ptr(A) if inspect else None, _ptr(b) if inspect else None,
+                                            self._stream()), "phgpu_eft_schur")
+        return (A, b) if inspect else None
+
+    def eft_direction(self, stage):
+        """ROOT's solve, the back-substitution, the direction pass and its sums (phgpu_eft_direction);
+        stage 0 stores the iterate's test in ``ef_info``."""
+        self.calls["eft_direction"] += 1
+        if stage == 0:
+            self._ef_info_np[:] = np.nan
+        _lib.check(self.lib.phgpu_eft_direction(self.h, int(stage), ctypes.c_void_p(self.ef_info.data_ptr()), self._stream()),
+                   "phgpu_eft_direction")
+        if stage == 0:
+            self._ef_ev.record()
+
+    def eft_step(self, stage):
+        """Sigma (stage 0) or the step (stage 1) (phgpu_eft_step).  Device work only."""
+        self.calls["eft_step"] += 1
+        _lib.check(self.lib.phgpu_eft_step(self.h, int(stage), self._stream()), "phgpu_eft_step")
+
+    def eft_iteration(self):
+        """One predictor-corrector iteration on the tree: nothing is read on the host."""
+        for stage in (0, 1):
+            self.eft_schur(stage)
+            self.eft_direction(stage)
+            self.eft_step(stage)
+
+    def eft_read(self):
+        """The iteration's one read (``ef_read``: the same record)."""
+        return self.ef_read()
+
+    def eft_export(self):
+        """The iterate into ``x``, ``y``, ``obj``, ``bound``, ``status``, ``iters`` and ``ef_z`` [Ztot]
+        (phgpu_eft_export)."""
+        _lib.check(self.lib.phgpu_eft_export(self.h, _ptr(self.x), _ptr(self.y), _ptr(self.obj), _ptr(self.bound),
+                                             _ptr(self.status), _ptr(self.iters), _ptr(self.ef_z), self._stream()),
+                   "phgpu_eft_export")
+
     # -------------------------------------------------------------- bundles
     def bundle_init(self, seg_start, zlb, zub, ncomp, cmax, tol, ztol, qp):
         """The segmented interior point's store (phgpu_bundle_init): host arrays

@@ -5,7 +5,9 @@ Same constructor as the reference and ``solve()``.  The reference hands the scen
 parapint's Schur-complement interior point over MPI; here the whole method runs on the device
 (phgpu_ef_*, include/phgpu.h): a lane per scenario factors its own block, the only coupling is the
 nn x nn system in the ROOT nonants, and every rank solves that system from the same all-reduced
-bits.  Two-stage continuous problems (LPs and diagonal QPs), minimisation internally; a
+bits.  Two-stage continuous problems (LPs and diagonal QPs; a multistage tree is ``ExtensiveForm``'s,
+opt/ef.py, and is refused here as the reference's sc.py has one set of linking variables),
+minimisation internally; a
 maximisation model is negated as everywhere else.  Per iteration, one read of pinned memory.
 
 ``options`` is a dict: ``tol`` (relative KKT tolerance, default 1e-8), ``max_iter`` (default 100),
@@ -33,6 +35,10 @@ DEFAULT_MAX_ITER = 100
 
 
 class SchurComplement(SPOpt):
+    # the reference's sc.py couples the blocks through ONE set of linking variables; the subclass
+    # that eliminates along a scenario tree (opt/ef.py) says so here
+    _serves_trees = False
+
     # sc.py:59-87
     def __init__(self, options, all_scenario_names, scenario_creator, scenario_creator_kwargs=None,
                  all_nodenames=None, mpicomm=None, model_name=None, suppress_warnings=False):
@@ -43,7 +49,8 @@ class SchurComplement(SPOpt):
         options.setdefault("toc", False)
         super().__init__(options, all_scenario_names, scenario_creator, all_nodenames=all_nodenames, mpicomm=mpicomm,
                          scenario_creator_kwargs=scenario_creator_kwargs)
-        if self.multistage or self.batch.depth != 1:
+        self._tree = self.multistage or self.batch.depth != 1
+        if self._tree and not self._serves_trees:
             raise RuntimeError("the Schur-complement interior point serves two-stage problems only "
                                f"({len(self.all_nodenames)} tree nodes)")
         if options.get("shared_matrix"):
@@ -108,17 +115,22 @@ class SchurComplement(SPOpt):
             raise NotImplementedError("a shared-matrix handle has no per-scenario matrix to factor")
         data = self._problem_data()
         e.fix_nonants(None)
-        e.ef_init(*data[:6], self.tol, data[6])
-        self.is_qp = data[6]
+        if self._tree:
+            e.eft_init(*data[0], *data[1:7], self.tol, data[7])
+        else:
+            e.ef_init(*data[:6], self.tol, data[6])
+        self.is_qp = data[-1]
 
     def _run(self):
         """The iterations; True when the iterate passes the test."""
         self._setup()
         e = self.engine
+        iteration, schur, direction, export = ((e.eft_iteration, e.eft_schur, e.eft_direction, e.eft_export) if self._tree
+                                               else (e.ef_iteration, e.ef_schur, e.ef_direction, e.ef_export))
         t0 = time.perf_counter()
         self.history, done, r = [], False, None
         for _ in range(self.max_iter):
-            e.ef_iteration()
+            iteration()
             r = e.ef_read()
             self.history.append(r)
             if self.verbose and self.cylinder_rank == 0:
@@ -128,12 +140,12 @@ class SchurComplement(SPOpt):
             if done or not math.isfinite(r["mu"]):
                 break
         else:
-            e.ef_schur(0)             # the test of the last iterate (nothing steps)
-            e.ef_direction(0)
+            schur(0)                  # the test of the last iterate (nothing steps)
+            direction(0)
             r = e.ef_read()
             self.history.append(r)
             done = r["done"] == 1.0
-        e.ef_export()
+        export()
         torch.cuda.synchronize(e.device)
         self.seconds = time.perf_counter() - t0
         self.iterations = int(r["iter"]) if r is not None and math.isfinite(r["iter"]) else len(self.history)
@@ -152,8 +164,8 @@ class SchurComplement(SPOpt):
         return self.status
 
     def root_nonants(self):
-        """z, the ROOT nonants of the last solve (host [nn])."""
-        return self.engine.ef_z.cpu().numpy()
+        """z, the ROOT nonants of the last solve (host [nlens[0]])."""
+        return self.engine.ef_z.cpu().numpy()[:int(self.batch.nlens()[0])]
 
     def objective_value(self):
         """The extensive form's objective at the last iterate, in the model's sense."""

@@ -24,6 +24,10 @@
  *                                          mpisppy/opt/ef.py:60-140, opt/sc.py:60-105 -> phgpu_ef_*
  *   - bundles: the extensive form of each bundle's scenarios as a PH subproblem
  *                                          mpisppy/spbase.py:219-253, spopt.py:805-836 -> phgpu_bundle_*
+ *   - the extensive form of a scenario tree (create_EF with all_nodenames), and of a sampled subtree
+ *     whose ancestors' nonants are fixed (SampleSubtree fixing its Vars; every subtree of a stage in
+ *     one conditioned tree)              mpisppy/confidence_intervals/sample_tree.py:79-158, 234-251
+ *                                          -> phgpu_eft_*, phgpu_eft_fix
  *   - the per-batch moments of the MMW gap estimators and of zhat4xhat
  *                                          mpisppy/confidence_intervals/ciutils.py:400-415 -> phgpu_gap_moments
  *   - APH's projective step, dispatch and partial solve loop (Update_y, Compute_Averages,
@@ -909,7 +913,10 @@ int phgpu_bundle_export(phgpu_handle h, double* x, double* y, double* obj, doubl
  * of the tree and is eliminated bottom-up, a wave per node; ROOT's block is solved as phgpu_ef_*
  * solves C.  One rank; all entries are ordered on the stream, none synchronises, no floating-point
  * atomics: the same input gives the same bits.  An iteration is, per right-hand side,
- * phgpu_eft_schur -> phgpu_eft_direction -> phgpu_eft_step.
+ * phgpu_eft_schur -> phgpu_eft_direction -> phgpu_eft_step.  Between phgpu_eft_init and the first
+ * phgpu_eft_schur, phgpu_eft_fix may hold any entries of z at given values: the CONDITIONED extensive
+ * form, which with every node above a stage held is the forest of that stage's
+ * subtrees in one solve.
  *
  * phgpu_eft_init: allocate the store (the handle's; freed by phgpu_destroy or another init) and set
  * the start.  HOST arrays: nlens [D] the nonants per depth (their sum is the handle's nn, whose
@@ -923,6 +930,19 @@ int phgpu_bundle_export(phgpu_handle h, double* x, double* y, double* obj, doubl
 int phgpu_eft_init(phgpu_handle h, int32_t D, const int32_t* nlens, int32_t Nn, const int32_t* node_depth,
                    const int32_t* node_parent, const int32_t* seg_start, const double* zlb, const double* zub,
                    const double* cz, const double* qz, double ncomp, double cmax, double tol, int32_t qp, void* stream);
+
+/* Hold entries of z at values (sample_tree.py: the extensive form of a subtree with its ancestors'
+ * nonants fixed).  zfix: HOST [Ztot], NaN = the entry stays free.  Once, after phgpu_eft_init and
+ * before the first phgpu_eft_schur (another phgpu_eft_init starts over).  A held entry keeps the
+ * value's bits to the export: its dz is exactly 0 in both right-hand sides of every iteration, it has
+ * no bound duals and takes no part in the complementarity (its finite bounds leave ncomp), in the dual
+ * residual of the test, in the step lengths or in the affine mu.  In its node's elimination its row
+ * and column are the identity's with right-hand side 0, so what the parent reads gets nothing from
+ * it; ROOT's likewise.  Any subset may be held, all of z included (the scenarios then only share mu
+ * and the step lengths).  A call with every entry NaN leaves the bits of a solve without it.
+ * -1: no store, an iteration has begun, a second call, a value that is not finite or lies outside
+ * the entry's [zlb, zub] (the message names the node and the entry). */
+int phgpu_eft_fix(phgpu_handle h, const double* zfix, void* stream);
 
 /* The scenario pass (phgpu_ef_schur's, on the scenario's whole path), the segmented sums of its
  * terms per deepest node (a thread or, for long segments, a block per value and segment; index

@@ -63,6 +63,11 @@ EF_FN double ef_inside(double lo, double hi) {
     return 0.0;
 }
 
+// A z entry held at a value (phgpu_eft_fix; DESIGN.md 3.24) is stored with the empty box lo = +inf,
+// hi = -inf: neither side is finite, so wherever a box is read it has no slack, no dual, no
+// complementarity and no ratio, and this test tells it from a free entry.  Nothing else sets such a box.
+EF_FN bool ef_held(double lo, double hi) { return lo > hi; }
+
 // One boxed variable: value v in [lo, hi], duals zl zu, direction d.
 struct ef_box {
     bool fl, fu;
@@ -441,7 +446,7 @@ EF_FN void ef_solve_core(const ef_store& E, int stage, const double* rsum, const
             for (int k = 0; k < nn; ++k) {
                 const ef_box b = ef_mkbox(z[k], zlb[k], zub[k], zlz[k], zuz[k]);
                 comp += (b.fl ? b.sl * b.zl : 0.0) + (b.fu ? b.su * b.zu : 0.0);
-                rzm = fmax(rzm, fabs(cz[k] + qz[k] * z[k] - ty[k] - zlz[k] + zuz[k]));
+                if (!ef_held(zlb[k], zub[k])) rzm = fmax(rzm, fabs(cz[k] + qz[k] * z[k] - ty[k] - zlz[k] + zuz[k]));
             }
             const double obj = rsum[ntri + 2 * nn + 1];
             const double mu = comp / E.ctl[EC_NCOMP];
@@ -473,6 +478,12 @@ EF_FN void ef_solve_core(const ef_store& E, int stage, const double* rsum, const
         }
         LS_SYNC();
         for (int k = LS_TID; k < nn; k += LS_NT) {
+            if (ef_held(zlb[k], zub[k])) {  // its row and column: the identity's (off the diagonal, so no
+                for (int j = 0; j < k; ++j) M[k * ld + j] = 0.0;       // other thread's entry; where two held
+                for (int i = k + 1; i < nn; ++i) M[i * ld + k] = 0.0;  // entries meet both store the same 0)
+                M[k * ld + k] = 1.0;
+                continue;
+            }
             const ef_box b = ef_mkbox(z[k], zlb[k], zub[k], zlz[k], zuz[k]);
             const double d = M[k * ld + k] + qz[k] + ef_theta(b);
             M[k * ld + k] = d + EF_REG * d;
@@ -493,12 +504,12 @@ EF_FN void ef_solve_core(const ef_store& E, int stage, const double* rsum, const
         ef_targets(stage, sigmu, b, dza[k], false, 0.0, tl, tu);
         const double tyk = stage == 0 ? rsum[ntri + nn + k] : ty[k];
         if (stage == 0) EF_Z(E, EZ_N)[k] = tyk;
-        rhs[k] = -(cz[k] + qz[k] * z[k] - tyk - ef_push(b, tl, tu)) + ng[k];
+        rhs[k] = ef_held(zlb[k], zub[k]) ? 0.0 : -(cz[k] + qz[k] * z[k] - tyk - ef_push(b, tl, tu)) + ng[k];
     }
     LS_SYNC();
     ls_fwd(M, nn, ld, rhs);
     ls_bwd(M, nn, ld, rhs);
-    for (int k = LS_TID; k < nn; k += LS_NT) dz[k] = rhs[k];
+    for (int k = LS_TID; k < nn; k += LS_NT) dz[k] = ef_held(zlb[k], zub[k]) ? 0.0 : rhs[k];
 }
 
 // One wave, after the ranks' sums and maxima of a direction pass.  stage 0: the affine step
@@ -535,6 +546,7 @@ EF_FN void ef_ctrl_core(const ef_store& E, int stage, const double* rsum, const 
         return;
     }
     for (int k = 0; k < nn; ++k) {
+        if (ef_held(zlb[k], zub[k])) continue;  // (z keeps its bits, a -0.0 included)
         const ef_box b = ef_mkbox(z[k], zlb[k], zub[k], zlz[k], zuz[k]);
         double tl, tu, dl, du;
         ef_targets(1, sigmu, b, dza[k], false, 0.0, tl, tu);

@@ -90,8 +90,22 @@ EF_FN void eft_node_load(const eft_tree& T, int n, int stage, double* M, double*
 EF_FN void eft_node_zside(const eft_tree& T, const double* ctl, int n, int stage, double* M, double* b, const double* ty) {
     const int d = T.depth[n], nl = T.P[d] - (d ? T.P[d - 1] : 0), ld = T.ld;
     const double sigmu = ctl[EC_SIGMU];
+    const int P = T.P[d];
     for (int k = LS_TID; k < nl; k += LS_NT) {
         const int zi = T.zoff[n] + k;
+        if (ef_held(*eft_zp(T, EZ_LB, zi), *eft_zp(T, EZ_UB, zi))) {
+            // A held entry (3.24): its row and column of the node's own block are the identity's and
+            // its right-hand side 0, in both stages; the trailing block and h_n then get nothing from it.
+            // (Off the diagonal, so no other thread's entry; where two held entries meet both store the same 0.)
+            if (stage == 0) {
+                for (int j = 0; j < k; ++j) M[k * ld + j] = 0.0;
+                for (int i = k + 1; i < P; ++i) M[i * ld + k] = 0.0;
+                M[k * ld + k] = 1.0;
+                *eft_zp(T, EZ_N, zi) = ty[k];
+            }
+            b[k] = 0.0;
+            continue;
+        }
         const double z = *eft_zp(T, EZ_Z, zi), cz = *eft_zp(T, EZ_C, zi), qz = *eft_zp(T, EZ_Q, zi);
         const ef_box bx = ef_mkbox(z, *eft_zp(T, EZ_LB, zi), *eft_zp(T, EZ_UB, zi), *eft_zp(T, EZ_ZL, zi), *eft_zp(T, EZ_ZU, zi));
         if (stage == 0) {
@@ -110,6 +124,7 @@ EF_FN void eft_node_zside(const eft_tree& T, const double* ctl, int n, int stage
             const int zi = T.zoff[n] + k;
             const double z = *eft_zp(T, EZ_Z, zi), zl = *eft_zp(T, EZ_ZL, zi), zu = *eft_zp(T, EZ_ZU, zi);
             const ef_box bx = ef_mkbox(z, *eft_zp(T, EZ_LB, zi), *eft_zp(T, EZ_UB, zi), zl, zu);
+            if (ef_held(*eft_zp(T, EZ_LB, zi), *eft_zp(T, EZ_UB, zi))) continue;
             comp += (bx.fl ? bx.sl * bx.zl : 0.0) + (bx.fu ? bx.su * bx.zu : 0.0);
             rzm = fmax(rzm, fabs(*eft_zp(T, EZ_C, zi) + *eft_zp(T, EZ_Q, zi) * z - ty[k] - zl + zu));
         }
@@ -186,6 +201,10 @@ EF_FN void eft_node_back(const eft_tree& T, int n) {
     const double* slot = EFT_SLOT(T, n);
     double* dz = eft_zp(T, EZ_DZ, T.zoff[n]);
     for (int j = nl - 1; j >= 0; --j) {
+        if (ef_held(*eft_zp(T, EZ_LB, T.zoff[n] + j), *eft_zp(T, EZ_UB, T.zoff[n] + j))) {
+            dz[j] = 0.0;  // (exactly: its column is the identity's)
+            continue;
+        }
         double a = T.hv[(size_t)n * T.nn + j];
         for (int i = j + 1; i < nl; ++i) a -= slot[(size_t)i * ld + j] * dz[i];
         for (int k = 0; k < Pp; ++k) a -= slot[(size_t)(nl + k) * ld + j] * *eft_zp(T, EZ_DZ, T.path[(size_t)n * T.nn + k]);
@@ -195,6 +214,7 @@ EF_FN void eft_node_back(const eft_tree& T, int n) {
 
 // what z entry zi (not ROOT's) gives to the step lengths and the affine mu
 EF_FN void eft_z_ratios(const eft_tree& T, const double* ctl, int stage, int zi, double& rp, double& rd, double (&ct)[3]) {
+    if (ef_held(*eft_zp(T, EZ_LB, zi), *eft_zp(T, EZ_UB, zi))) return;
     const ef_box b = ef_mkbox(*eft_zp(T, EZ_Z, zi), *eft_zp(T, EZ_LB, zi), *eft_zp(T, EZ_UB, zi), *eft_zp(T, EZ_ZL, zi),
                               *eft_zp(T, EZ_ZU, zi));
     const double dz = *eft_zp(T, EZ_DZ, zi);
@@ -205,7 +225,7 @@ EF_FN void eft_z_ratios(const eft_tree& T, const double* ctl, int stage, int zi,
 }
 // z entry zi (not ROOT's) after ef_ctrl_core: stage 0 keeps the affine dz, stage 1 takes the step
 EF_FN void eft_z_step(const eft_tree& T, const double* ctl, int stage, int zi) {
-    if (ctl[EC_DONE] != 0.0) return;
+    if (ctl[EC_DONE] != 0.0 || ef_held(*eft_zp(T, EZ_LB, zi), *eft_zp(T, EZ_UB, zi))) return;  // (a held z keeps its bits)
     const double dz = *eft_zp(T, EZ_DZ, zi);
     if (stage == 0) {
         *eft_zp(T, EZ_DZA, zi) = dz;

@@ -3568,6 +3568,12 @@ struct eft_store {
     int block_reduce;            // the segmented sum by a block per (plane, segment)
     std::vector<int> lvl0;       // [D + 1]: the first node of each depth
     std::vector<int> Ph;         // [D]: P_d on the host
+    // for phgpu_eft_fix: the z fields as uploaded (zn: [EZ_N + 1][Ztot], rz: ROOT's [EZ_N + 1][P0]),
+    // each entry's node, the count of finite bounds, and where the solve stands
+    std::vector<double> zn, rz;
+    std::vector<int> znode;
+    double ncomp;
+    bool held, begun;
 };
 
 static void eft_release(phgpu_state* h) {
@@ -3701,6 +3707,13 @@ extern "C" int phgpu_eft_init(phgpu_handle h, int32_t D, const int32_t* nlens, i
     std::vector<int32_t> seg_of(S), depth(node_depth, node_depth + Nn);
     for (int g = 0; g < G; ++g)
         for (int32_t s = seg_start[g]; s < seg_start[g + 1]; ++s) seg_of[s] = g;
+    X->znode.resize(Ztot);
+    for (int i = 0; i < Nn; ++i)
+        for (int k = 0; k < nlens[node_depth[i]]; ++k) X->znode[zoff[i] + k] = i;
+    X->zn = zn;
+    X->rz = rz;
+    X->ncomp = ncomp;
+    X->held = X->begun = false;
     if (!rc) rc = ls_upload(h, &T->zn, zn.data(), zn.size());
     if (!rc) rc = ls_upload(h, &T->rootzd, rz.data(), rz.size());
     if (!rc) rc = ls_upload(h, &E->ctl, ctl.data(), ctl.size());
@@ -3753,9 +3766,54 @@ extern "C" int phgpu_eft_init(phgpu_handle h, int32_t D, const int32_t* nlens, i
 #define EFT_GATHER(X, f, st) \
     hipLaunchKernelGGL(k_eft_gather, dim3((unsigned)(((X).T.G * (X).T.nn + EF_T - 1) / EF_T)), dim3(EF_T), 0, st, (X).E, (X).T, (int)(f))
 
+// Entries of z held at values: the empty box (ef_held), the value, no duals; the
+// fields go up again whole from the store's host copies, which live as long as the store.
+extern "C" int phgpu_eft_fix(phgpu_handle h, const double* zfix, void* stream) {
+    EFT_READY(h, "phgpu_eft_fix", 0);
+    if (!zfix) return set_err(-1, "null argument");
+    eft_store& X = *h->eft;
+    const eft_tree& T = X.T;
+    if (X.begun) return set_err(-1, "phgpu_eft_fix: an iteration has begun (it comes before the first phgpu_eft_schur)");
+    if (X.held) return set_err(-1, "phgpu_eft_fix: called twice (phgpu_eft_init starts over)");
+    const int Ztot = T.Ztot, P0 = T.P0;
+    auto fld = [&](int f, int k) -> double& {
+        return k < P0 ? X.rz[(size_t)f * P0 + k] : X.zn[(size_t)f * Ztot + k];
+    };
+    for (int k = 0; k < Ztot; ++k) {
+        const double v = zfix[k];
+        if (v != v) continue;
+        if (isfinite(v) && v >= fld(EZ_LB, k) && v <= fld(EZ_UB, k)) continue;
+        const int nd = X.znode[k];
+        int e = 0;  // the entry's place in its node
+        while (e < k && X.znode[k - e - 1] == nd) ++e;
+        return set_err(-1, "phgpu_eft_fix: node %d entry %d: the value %.17g is outside its bounds [%g, %g]", nd, e, v,
+                       fld(EZ_LB, k), fld(EZ_UB, k));
+    }
+    double ncomp = X.ncomp;
+    for (int k = 0; k < Ztot; ++k) {
+        const double v = zfix[k];
+        if (v != v) continue;
+        ncomp -= (isfinite(fld(EZ_LB, k)) ? 1.0 : 0.0) + (isfinite(fld(EZ_UB, k)) ? 1.0 : 0.0);
+        fld(EZ_LB, k) = INFINITY;
+        fld(EZ_UB, k) = -INFINITY;
+        fld(EZ_Z, k) = v;
+        fld(EZ_ZL, k) = fld(EZ_ZU, k) = 0.0;
+    }
+    X.ncomp = fmax(1.0, ncomp);
+    X.held = true;
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipMemcpyAsync(T.zn, X.zn.data(), X.zn.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(T.rootzd, X.rz.data(), X.rz.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(X.E.ctl + EC_NCOMP, &X.ncomp, sizeof(double), hipMemcpyHostToDevice, st));
+    EFT_GATHER(X, EZ_Z, st);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // the scenario pass, its segmented sums, the elimination up the tree and ROOT's sums
 extern "C" int phgpu_eft_schur(phgpu_handle h, int32_t stage, double* nodeA, double* nodeb, void* stream) {
     EFT_READY(h, "phgpu_eft_schur", stage);
+    h->eft->begun = true;
     hipStream_t st = (hipStream_t)stream;
     const eft_store& X = *h->eft;
     const ef_store& E = X.E;

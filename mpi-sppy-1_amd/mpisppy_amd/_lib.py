@@ -92,7 +92,8 @@ EXPORTS = ["phgpu_default_options", "phgpu_create", "phgpu_create2", "phgpu_set_
            "phgpu_ef_init", "phgpu_ef_schur", "phgpu_ef_direction", "phgpu_ef_step", "phgpu_ef_export",
            "phgpu_bundle_init", "phgpu_bundle_start", "phgpu_bundle_schur", "phgpu_bundle_direction",
            "phgpu_bundle_step", "phgpu_bundle_export",
-           "phgpu_eft_init", "phgpu_eft_schur", "phgpu_eft_direction", "phgpu_eft_step", "phgpu_eft_export"]
+           "phgpu_eft_init", "phgpu_eft_schur", "phgpu_eft_direction", "phgpu_eft_step", "phgpu_eft_export",
+           "phgpu_eft_fix"]
 
 _lib = None
 
@@ -182,6 +183,7 @@ def load(path=None):
     lib.phgpu_bundle_export.argtypes = [c_vp] + [c_vp] * 7
     lib.phgpu_eft_init.argtypes = [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_dbl,
                                    c_i32, c_vp]
+    lib.phgpu_eft_fix.argtypes = [c_vp, c_vp, c_vp]
     lib.phgpu_eft_schur.argtypes = [c_vp, c_i32, c_vp, c_vp, c_vp]
     lib.phgpu_eft_direction.argtypes = [c_vp, c_i32, c_vp, c_vp]
     lib.phgpu_eft_step.argtypes = [c_vp, c_i32, c_vp]

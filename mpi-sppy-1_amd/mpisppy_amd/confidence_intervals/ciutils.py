@@ -1,6 +1,8 @@
 """Utilities of the confidence-interval package (mirrors mpisppy/confidence_intervals/ciutils.py;
 DESIGN.md 3.20): the Mak-Morton-Wood gap estimators G and s of [bm2011] section 2 at a candidate
-x̂, the xhat files, and a Student-t quantile.  Two-stage problems only.
+x̂, the xhat files, and a Student-t quantile.  Two-stage problems, and multistage ones
+(``EF_mstage``) through ``sample_tree.py``: one free tree extensive form, one conditioned extensive
+form per interior stage and the same two batched evaluations.
 
 The reference computes one estimator at a time: an extensive-form solve for the sample problem's
 optimum x*, then two Xhat_Eval passes and a host loop over the scenarios (ciutils.py:335-415).
@@ -16,8 +18,9 @@ own, and ``ef_xstar_solver`` makes one that does solve the extensive form (opt/e
 they sum to the number of batches: every moment is divided by its segment's sum of probabilities,
 and no result depends on their common scale.  A scenario that is not solved to optimality in
 either solve raises (an estimator over a subset of its sample is not the estimator); the
-reference would carry on with whatever the solver left.  ``EF_mstage`` (sample_tree.py) raises
-NotImplementedError.
+reference would carry on with whatever the solver left.  ``EF_mstage`` on a model module without
+``sample_tree_scen_creator`` raises NotImplementedError naming it (the reference: RuntimeError, from
+SampleSubtree's constructor), before ``sample_options`` is looked at.
 """
 import importlib
 import math
@@ -28,7 +31,7 @@ import numpy as np
 
 from .. import global_toc
 from ..comm import Comm
-from ..sputils import extract_num
+from ..sputils import extract_num, number_of_nodes, create_nodenames_from_branching_factors
 
 MINIMIZE, MAXIMIZE = 1, -1          # pyo.minimize, pyo.maximize
 
@@ -103,6 +106,65 @@ def check_module(m):
                if not hasattr(m, fct)]
     if missing:
         raise RuntimeError(f"Module {getattr(m, '__name__', m)} not complete for from_module (missing: {missing})")
+
+
+# ------------------------------------------------------------------ sample trees (ciutils.py:25-133)
+def _prime_factors(n):
+    """{prime: multiplicity} of n >= 1, the primes ascending."""
+    if n < 1:
+        raise ValueError(f"_prime_factors require positive input ({n})")
+    out, p = {}, 2
+    while p * p <= n:
+        while n % p == 0:
+            out[p] = out.get(p, 0) + 1
+            n //= p
+        p += 1 if p == 2 else 2
+    if n > 1:
+        out[n] = out.get(n, 0) + 1
+    return out
+
+
+def branching_factors_from_numscens(numscens, num_stages):
+    """Branching factors of a balanced sample tree with about ``numscens`` leaves: the prime factors
+    of the first of numscens, numscens + 1, ... that has at least num_stages - 1 of them, dealt
+    round-robin to the stages (ciutils.py:54-84).  None for two stages."""
+    if num_stages == 2:
+        return None
+    k = num_stages - 1
+    for i in range(2 ** k):
+        pf = _prime_factors(numscens + i) if numscens + i >= 1 else {}
+        if sum(pf.values()) >= k:
+            facts = [f for f, mult in pf.items() for _ in range(mult)]
+            return [int(np.prod(facts[j::k])) for j in range(k)]
+    raise RuntimeError("branching_factors_from_numscens is not working correctly.")
+
+
+def scalable_branching_factors(numscens, ref_branching_factors):
+    """Branching factors of a tree with at least ``numscens`` leaves shaped like
+    ``ref_branching_factors``, the first stages rounded up first: 233 with [5, 3, 2] gives [10, 6, 4]
+    (ciutils.py:86-123)."""
+    k = len(ref_branching_factors)
+    if numscens < 2 ** k:
+        return [2] * k
+    mult = (numscens / np.prod(ref_branching_factors)) ** (1 / k)
+    new = np.maximum(np.floor(np.array(ref_branching_factors) * mult), 1.0)
+    i = 0
+    while np.prod(new) < numscens:
+        if i == k:
+            raise RuntimeError("scalable branching_factors is failing")
+        new[i] += 1
+        i += 1
+    return [int(v) for v in new]
+
+
+def is_sorted(nodelist):
+    """ciutils.py:125-133: a scenario's node list runs ROOT, its child, ... one node per stage."""
+    parent = None
+    for t, node in enumerate(nodelist):
+        if t + 1 != node.stage or node.parent_name != parent:
+            raise RuntimeError(f"The node list is not well-constructed: the stage {node.stage} node {node.name} (parent "
+                               f"{node.parent_name}) is element {t + 1} of the list, after {parent}")
+        parent = node.name
 
 
 # ------------------------------------------------------------------ xhat files (ciutils.py:135-164)
@@ -460,8 +522,8 @@ def gap_estimators(xhat_one, mname, solving_type="EF_2stage", scenario_names=Non
     if solving_type not in ("EF_2stage", "EF_mstage"):
         raise RuntimeError("Only EF solve for the approximate problem is supported yet.")
     if solving_type == "EF_mstage":
-        raise NotImplementedError("EF_mstage needs sample_tree (SampleSubtree, walking_tree_xhats), which this "
-                                  "engine does not serve: two-stage problems only")
+        return _gap_estimators_mstage(xhat_one, mname, sample_options, ArRP, cfg, scenario_denouement, solver_name,
+                                      solver_options, verbose, mpicomm, info)
     if not scenario_names:
         raise RuntimeError("gap_estimators needs scenario_names for a two-stage problem")
     names = list(scenario_names)
@@ -470,3 +532,87 @@ def gap_estimators(xhat_one, mname, solving_type="EF_2stage", scenario_names=Non
                                solver_options=solver_options, verbose=verbose, mpicomm=mpicomm,
                                xstar_solver=xstar_solver, scenario_names=names, info=info)
     return {"G": float(r["G"][0]), "s": float(r["s"][0]), "seed": r["seed"]}
+
+
+def _gap_estimators_mstage(xhat_one, mname, sample_options, ArRP, cfg, scenario_denouement, solver_name, solver_options,
+                           verbose, mpicomm, info):
+    """ciutils.py:319-427 for ``EF_mstage``: the sample tree at ``seed`` and its free extensive form
+    (zn_star, xstars), ``walking_tree_xhats`` from ``xhat_one["ROOT"]`` with the seed advanced past
+    the sample tree, then Xhat_Eval over the sample tree at xhats and at xstars and the moments of
+    the two objective arrays in one ``engine.gap_moments`` read.  ``info`` (a dict) receives
+    "iterations" {"free": n, "conditioned": [n per stage]}, "seconds" {"free", "conditioned",
+    "evaluations"}, "xhats", "zn_star" and the per-scenario objective arrays "f_hat", "f_star"
+    (host, the model's sense)."""
+    import torch
+    from ..utils.xhat_eval import Xhat_Eval
+    from . import sample_tree
+    m = model_module(mname)
+    if not hasattr(m, "sample_tree_scen_creator"):
+        raise NotImplementedError(f"EF_mstage needs a model module with sample_tree_scen_creator (sample_tree.py); "
+                                  f"{getattr(m, '__name__', m)} has none")
+    check_module(m)
+    try:
+        branching_factors = list(sample_options["branching_factors"])
+        start = int(sample_options["seed"])
+    except (TypeError, KeyError):
+        raise RuntimeError("For multistage problems, sample_options must be a dict with branching_factors and seed "
+                           "attributes.") from None
+    if ArRP > 1:
+        raise RuntimeError("Pooled estimators are not supported for multistage problems yet.")
+    lcfg = CfgView(cfg)
+    if solver_name is None:
+        solver_name = lcfg.get("EF_solver_name", lcfg.get("solver_name"))
+    _, sp_options = _split_solver_options(lcfg, solver_options)
+    secs = {}
+    tick = time.perf_counter()
+
+    def lap(key):
+        nonlocal tick
+        torch.cuda.synchronize()
+        secs[key] = secs.get(key, 0.0) + time.perf_counter() - tick
+        tick = time.perf_counter()
+
+    samp_tree = sample_tree.SampleSubtree(m, [], None, 1, branching_factors, start, cfg, solver_name, solver_options)
+    ev = None
+    try:
+        samp_tree.run()
+        lap("free")
+        start += number_of_nodes(branching_factors)
+        zn_star = samp_tree.best_outer_bound
+        xstars = {nd: np.array(v, dtype=np.float64) for nd, v in samp_tree.ef.tree_nonants()}
+        walk = {}
+        xhats, start = sample_tree.walking_tree_xhats(m, dict(samp_tree.ef.scenarios()), xhat_one["ROOT"], branching_factors,
+                                                      start, cfg, solver_name=solver_name, solver_options=solver_options,
+                                                      info=walk)
+        lap("conditioned")
+        nodenames = create_nodenames_from_branching_factors(branching_factors) if len(branching_factors) > 1 else None
+        ev = Xhat_Eval({"solver_name": solver_name, "toc": False, "verbose": False, "device": lcfg.get("device"),
+                        "solver_options": sp_options}, samp_tree.scenario_names, samp_tree.scenario_creator,
+                       scenario_denouement, scenario_creator_kwargs=samp_tree.kwargs, all_nodenames=nodenames, mpicomm=mpicomm)
+        ev._lazy_create_solvers()
+        e = ev.engine
+        ev._fix_nonants(xhats)
+        ev.solve_loop(solver_options=sp_options)
+        f_hat, st_hat = e.obj.clone(), e.status.clone()
+        ev._fix_nonants(xstars)
+        ev.solve_loop(solver_options=sp_options)
+        M = e.gap_moments(np.array([0, len(samp_tree.scenario_names)], dtype=np.int64), f_hat, st_hat, e.obj, e.status)
+        sense = ev.batch.sense
+        if info is not None:
+            info["f_hat"], info["f_star"] = sense * f_hat.cpu().numpy(), sense * e.obj.cpu().numpy()
+        lap("evaluations")
+    finally:
+        samp_tree.close()
+        if ev is not None and ev.engine is not None:
+            ev.engine.close()
+    if M[0, 6] > 0:
+        raise RuntimeError(f"{int(M[0, 6])} scenario(s) of the sample tree were not solved to optimality at the policy or at "
+                           f"x*; the estimator needs its whole sample")
+    est = moments_to_estimators(M, sense, lcfg)      # (G, s with 1 - sum p^2, correcting_numeric: as two-stage)
+    G, s = float(est["G"][0]), float(est["s"][0])
+    if info is not None:
+        info.update({"iterations": {"free": samp_tree.ef.iterations, "conditioned": walk.get("iterations", [])},
+                     "seconds": secs, "xhats": xhats, "zn_star": zn_star, "walk": walk})
+    if verbose and (mpicomm is None or mpicomm.Get_rank() == 0):
+        global_toc(f"G = {G} s = {s}")
+    return {"G": G, "s": s, "seed": start}

@@ -1600,6 +1600,13 @@ class PHEngine:
         for k in ("eft_schur", "eft_direction", "eft_step"):
             self.calls[k] = 0
 
+    def eft_fix(self, zfix):
+        """Hold entries of z at values for the solve that follows (phgpu_eft_fix): host
+        ``zfix`` [Ztot] in node order, NaN where the entry stays free.  After ``eft_init``, before the
+        first ``eft_schur``."""
+        zfix = np.ascontiguousarray(np.asarray(zfix, dtype=np.float64).reshape(self.eft_ztot))
+        _lib.check(self.lib.phgpu_eft_fix(self.h, ctypes.c_void_p(zfix.ctypes.data), self._stream()), "phgpu_eft_fix")
+
     def eft_schur(self, stage, inspect=False):
         """The scenario pass, its sums per deepest node, the elimination up the tree and ROOT's sums
         (phgpu_eft_schur).  Device work only.  ``inspect``: returns device copies (A [Nn, nn, nn]

@@ -2,7 +2,9 @@
 
 ``scenario_creator`` restates aircond.py:88-330 for ``start_ups=False`` (the LP/QP
 case; start-up binaries are outside this engine's hot path) as a LinearModel;
-``batch_creator`` builds a rank's scenarios at once.
+``batch_creator`` builds a rank's scenarios at once.  For multistage sampling
+(confidence_intervals/sample_tree.py): ``sample_tree_scen_creator`` (aircond.py:332-374) and its
+vectorised form ``sample_forest_batch_creator``, which builds all subtrees of one stage at once.
 """
 import numpy as np
 
@@ -74,6 +76,14 @@ def scenario_creator(sname, **kwargs):
     kwargs = {**{k: v for k, v in PARMS.items() if k != "start_seed"}, **kwargs}
     bfs = list(kwargs["branching_factors"])
     demands, nodenames = demands_creator(sname, bfs, **kwargs)
+    mdl, st = _model_from_demands(sname, demands, kwargs)
+    mdl._mpisppy_node_list = _nodes_for_scen(mdl, st, nodenames, bfs)
+    mdl._mpisppy_probability = 1 / np.prod(bfs)
+    return mdl
+
+
+def _model_from_demands(sname, demands, kwargs):
+    """aircond_model_creator (aircond.py:184-249): the stage models and the material balance."""
     T = len(demands)
     cap = _kw(kwargs, "Capacity")
     bigM = cap * 25
@@ -101,19 +111,72 @@ def scenario_creator(sname, **kwargs):
         else:
             terms.append((st[t - 1][2], 1.0))
         mdl.row(terms, rhs, rhs, f"MaterialBalance[{t}]")
-    # MakeNodesforScen, aircond.py:251-302 (starting_stage=1)
+    mdl.demands = demands
+    mdl.stage_vars = st
+    return mdl, st
+
+
+def _nodes_for_scen(mdl, st, nodenames, bfs, starting_stage=1):
+    """MakeNodesforScen, aircond.py:251-302: up to ``starting_stage`` one node per stage (ROOT,
+    ROOT_0, ROOT_0_0, ...), below it the sample tree's."""
+    T = len(st)
     nodes = [ScenarioNode("ROOT", 1.0, 1, None, [st[1][0], st[1][1]], mdl)]
     ndn = "ROOT"
     for t in range(2, T):
         parent = ndn
-        ndn = parent + "_" + nodenames[t - 1]
-        nodes.append(ScenarioNode(ndn, 1.0 / bfs[t - 2], t, None, [st[t][0], st[t][1]], mdl,
-                                  parent_name=parent))
-    mdl._mpisppy_node_list = nodes
+        if t <= starting_stage:
+            ndn, cp = parent + "_0", 1.0
+        else:
+            ndn, cp = parent + "_" + nodenames[t - starting_stage], 1.0 / bfs[t - starting_stage - 1]
+        nodes.append(ScenarioNode(ndn, cp, t, None, [st[t][0], st[t][1]], mdl, parent_name=parent))
+    return nodes
+
+
+def sample_tree_scen_creator(sname, stage, sample_branching_factors, seed, given_scenario=None,
+                             **scenario_creator_kwargs):
+    """aircond.py:332-374: a scenario of the sample subtree that starts at ``stage``: the demands of
+    stages 1..stage are ``given_scenario``'s, the later ones are sampled with ``seed`` over
+    ``sample_branching_factors`` (as in the reference, that walk restarts from ``starting_d``, not
+    from the demand of the stage it starts at)."""
+    kw = {**{k: v for k, v in PARMS.items() if k != "start_seed"}, **scenario_creator_kwargs}
+    if _kw(kw, "start_ups"):
+        raise NotImplementedError("start_ups (binaries) is outside the LP/QP hot path")
+    if given_scenario is None:
+        if stage != 1:
+            raise RuntimeError("sample_tree_scen_creator for aircond needs a 'given_scenario' argument if the starting "
+                               "stage is greater than 1")
+        past = [_kw(kw, "starting_d")]
+    else:
+        past = list(given_scenario.demands[:stage])
+    bfs = list(sample_branching_factors)
+    future, nodenames = demands_creator(sname, bfs, root_name="ROOT" + "_0" * (stage - 1), **{**kw, "start_seed": seed})
+    mdl, st = _model_from_demands(sname, past + future[1:], kw)
     mdl._mpisppy_probability = 1 / np.prod(bfs)
-    mdl.demands = demands
-    mdl.stage_vars = st
+    mdl._mpisppy_node_list = _nodes_for_scen(mdl, st, nodenames, bfs, starting_stage=stage)
     return mdl
+
+
+def kw_creator(cfg, optionsin=None):
+    """aircond.py:421-457: the creators' keyword arguments from ``optionsin`` (which wins) and
+    ``cfg`` (a mapping or an object with the option names as attributes), else the defaults."""
+    options = optionsin if optionsin is not None else {}
+    if "kwargs" in options:
+        return options["kwargs"]
+
+    def look(name):
+        v = options.get(name)
+        if v is None:
+            v = cfg.get(name) if hasattr(cfg, "get") else getattr(cfg, name, None)
+        return v
+    kwargs = {"branching_factors": look("branching_factors")}
+    for name, default in PARMS.items():
+        v = look(name)
+        kwargs[name] = default if v is None else v
+    return kwargs
+
+
+def scenario_denouement(rank, scenario_name, scenario):
+    pass
 
 
 def scenario_names_creator(num_scens, start=None):
@@ -179,3 +242,57 @@ def batch_creator(scenario_names, **kwargs):
                          rep(tb.ub), rl, ru, rep(tb.q), rep(tb.obj_const), tb.nonant_col,
                          tb.nonant_depth, tb.nonant_off, node_of, nonleaf, prob, prob_coeff,
                          tb.sense, tb.var_names, tb.nonant_names)
+
+
+def sample_forest_batch_creator(tree_demands, stage, seeds, **kwargs):
+    """All sample subtrees that start at ``stage`` (>= 2) as ONE ScenarioBatch with the shape of the
+    sample tree itself (confidence_intervals/sample_tree.py), whose
+    ``branching_factors`` are among the keyword arguments.  ``tree_demands``
+    [prod(bf), T]: the sample tree's demands per scenario, in tree order; ``seeds``: the seed of each
+    node of that stage, in node order.  Scenario s of the result keeps the sample tree's demands of
+    stages 1..stage (its node's) and takes those of the later stages from
+    ``sample_tree_scen_creator`` with its node's seed; within a node the scenarios are in the
+    subtree's tree order (scenario number modulo the subtree's size, as ``demands_creator`` places
+    them).  The rows, columns, bounds and costs equal ``batch_from_models`` over those models array
+    for array; nodes and probabilities are the sample tree's (a subtree's own probabilities are these
+    over its node's)."""
+    kw = {**{k: v for k, v in PARMS.items() if k != "start_seed"}, **kwargs}
+    bfs = list(kw["branching_factors"])         # (the sample tree's, as batch_creator takes them)
+    t = int(stage)
+    T = len(bfs) + 1
+    if not 2 <= t < T:
+        raise RuntimeError(f"sample_forest_batch_creator: stage {t} of a {T}-stage tree has no subtrees to sample")
+    dem = np.array(tree_demands, dtype=np.float64)
+    S, sub = int(np.prod(bfs)), int(np.prod(bfs[t - 1:]))
+    if dem.shape != (S, T) or len(seeds) != S // sub:
+        raise RuntimeError(f"sample_forest_batch_creator: demands {dem.shape} for {S} scenarios of {T} stages, "
+                           f"{len(seeds)} seeds for {S // sub} nodes of stage {t}")
+    names = []
+    for j, seed in enumerate(seeds):
+        for pos in range(sub):
+            nm = f"scen{int(seed) + (pos - int(seed)) % sub}"
+            fut, _ = demands_creator(nm, bfs[t - 1:], root_name="ROOT" + "_0" * (t - 1), **{**kw, "start_seed": int(seed)})
+            dem[j * sub + pos, :t] = dem[j * sub, :t]
+            dem[j * sub + pos, t:] = fut[1:]
+            names.append(nm)
+    tmpl, _ = _model_from_demands(names[0], list(dem[0]), kw)
+    tmpl._mpisppy_node_list = _nodes_for_scen(tmpl, tmpl.stage_vars, ["ROOT"] + ["0"] * len(bfs), bfs)
+    tmpl._mpisppy_probability = 1.0 / S
+    nonleaf = [nd for nd in create_nodenames_from_branching_factors(bfs) if nd.count("_") < len(bfs)]
+    tb = batch_from_models([names[0]], [tmpl], node_names=nonleaf)
+    mb = np.arange(tb.m - T, tb.m)                  # the material balance rows, as in batch_creator
+    rl, ru = np.repeat(tb.rl, S, axis=0), np.repeat(tb.ru, S, axis=0)
+    rhs = dem.copy()
+    rhs[:, 0] -= _kw(kw, "BeginInventory")
+    rl[:, mb] = rhs
+    ru[:, mb] = rhs
+    first = np.concatenate([[0], np.cumsum([int(np.prod(bfs[:d])) for d in range(T - 2)])])   # first node id per depth
+    node_of = np.array([[first[d] + s // int(np.prod(bfs[d:])) for d in range(T - 1)] for s in range(S)], dtype=np.int32)
+    rep = lambda a: np.repeat(a, S, axis=0)  # noqa: E731
+    prob = np.full(S, 1.0 / S)
+    uncond = np.array([1.0] + [1.0 / np.prod(bfs[:d]) for d in range(1, T - 1)])
+    b = ScenarioBatch(names, tb.row_ptr, tb.col_idx, rep(tb.A_val), rep(tb.c), rep(tb.lb), rep(tb.ub), rl, ru, rep(tb.q),
+                      rep(tb.obj_const), tb.nonant_col, tb.nonant_depth, tb.nonant_off, node_of, nonleaf, prob,
+                      prob[:, None] / uncond[None, :], tb.sense, tb.var_names, tb.nonant_names)
+    b.demands = dem
+    return b

@@ -9,6 +9,10 @@ Pyomo model with a reference variable per nonant and hands it to ``options["solv
 ``options["solver"]`` names this engine (one of ``spopt.SOLVER_NAMES``) and no model of the whole
 is built: the scenarios stay a batch and the nonants are one vector z on the device.
 
+On a tree, ``fix_node_nonants`` holds the nonants of chosen nodes at given values for the solves that
+follow (the CONDITIONED extensive form, DESIGN.md 3.24: what sample_tree.py's SampleSubtree does by
+fixing its ancestors' Vars); ``node_objectives`` then gives every subtree's own objective.
+
 DEPARTURES.  Continuous problems; a tree must have all its scenarios at the same depth and the
 scenarios in tree order, so that every node's scenarios are contiguous (RuntimeError otherwise);
 the whole path has at most 64 nonants; ``bundles_per_rank`` raises NotImplementedError; ``solver_options`` takes ``tol`` and ``max_iter``.
@@ -119,16 +123,88 @@ class ExtensiveForm(SchurComplement):
                 np.minimum.at(zub, zi, b.ub[:, j])
                 np.add.at(cz, zi, b.prob * b.c[:, j])
                 np.add.at(qz, zi, b.prob * b.q[:, j])
-        if not np.all(zlb < zub):
-            k = int(np.nonzero(~(zlb < zub))[0][0])
+        held = self._held_z()
+        free = np.ones(Ztot, dtype=bool) if held is None else np.isnan(held)
+        if not np.all(zlb[free] < zub[free]):
+            k = int(np.flatnonzero(free & ~(zlb < zub))[0])
             nd = int(np.searchsorted(zoff, k, side="right") - 1)
             raise NotImplementedError(f"nonant {k - zoff[nd]} of node {b.node_names[nd]} has the bounds [{zlb[k]}, {zub[k]}] over "
                                       f"its scenarios: a fixed column leaves the interior point no interior")
+        # an entry held through fix_node_nonants needs no interior: where its bounds coincide at its
+        # value, phgpu_eft_init (which asks zlb < zub of every entry) gets a box around them
+        if held is not None:
+            shut = (zlb == zub) & (held == zlb)
+            zlb[shut] -= 1.0
+            zub[shut] += 1.0
         oth = np.setdiff1d(np.arange(b.n), nc)
         ranged = b.rl < b.ru
+        # (ncomp counts every z entry's finite bounds, as phgpu_eft_init takes it; phgpu_eft_fix leaves
+        # the held entries' out again)
         ncomp = (np.isfinite(b.lb[:, oth]).sum() + np.isfinite(b.ub[:, oth]).sum() + (np.isfinite(b.rl) & ranged).sum()
                  + (np.isfinite(b.ru) & ranged).sum() + np.isfinite(zlb).sum() + np.isfinite(zub).sum())
         return layout, zlb, zub, cz, qz, float(ncomp), float(np.abs(b.c).max(initial=0.0)), bool(np.any(b.q))
+
+    # ------------------------------------------------------------------ the conditioned extensive form
+    def fix_node_nonants(self, cache):
+        """Hold the nonants of nodes at values in every ``solve_extensive_form`` that follows:
+        ``cache`` is {node name: values}; a node that is missing and an entry that is NaN stay free.
+        After the solve ``nonants()`` and ``tree_nonants()`` return the held values bit for bit.
+        ``free_node_nonants()`` undoes it.  A two-stage problem (phgpu_ef_*) is not served."""
+        if not self._tree:
+            raise NotImplementedError("fix_node_nonants serves the multistage extensive form only: with ROOT's nonants "
+                                      "held a two-stage problem is S separate scenario problems (Xhat_Eval)")
+        b = self.batch
+        nlens, depth, _, _ = self._tree_layout()
+        fix = {}
+        for nd, vals in dict(cache).items():
+            if nd not in b.node_names:
+                raise RuntimeError(f"fix_node_nonants: {nd} is not a non-leaf node of the tree")
+            if vals is None:
+                continue
+            v = np.array(vals, dtype=np.float64).reshape(-1)
+            want = int(nlens[depth[list(b.node_names).index(nd)]])
+            if len(v) != want:
+                raise RuntimeError(f"fix_node_nonants: node {nd} has {want} nonants, {len(v)} values given")
+            fix[nd] = v
+        self._node_fix = fix or None
+
+    def free_node_nonants(self):
+        self._node_fix = None
+
+    def _held_z(self):
+        fix = getattr(self, "_node_fix", None)
+        if not fix:
+            return None
+        nlens, depth, _, _ = self._tree_layout()
+        zoff = np.concatenate([[0], np.cumsum(nlens[depth])])
+        z = np.full(int(zoff[-1]), np.nan)
+        names = list(self.batch.node_names)
+        for nd, v in fix.items():
+            n = names.index(nd)
+            z[zoff[n]:zoff[n + 1]] = v
+        return None if np.all(np.isnan(z)) else z
+
+    def node_objectives(self, depth):
+        """Per node of tree depth ``depth`` (0: ROOT), in node order: (node name, sum of p_s f_s over
+        the node's scenarios / the node's probability) of the last solve -- with the nodes above held,
+        the objective of that node's subtree alone (sample_tree.py's EF_Obj).  One read of the
+        exported per-scenario objectives, summed in index order."""
+        if self.status is None:
+            raise ValueError("the extensive form has not been solved")
+        b = self.batch
+        if not 0 <= depth < b.depth:
+            raise ValueError(f"depth {depth} (the tree has the non-leaf depths 0..{b.depth - 1})")
+        f = b.sense * self.engine.obj.cpu().numpy()
+        ids = np.asarray(b.node_of)[:, depth]
+        out = []
+        for n in np.unique(ids):
+            ss = np.flatnonzero(ids == n)
+            num = den = 0.0
+            for s in ss:
+                num += b.prob[s] * f[s]
+                den += b.prob[s]
+            out.append((b.node_names[n], num / den))
+        return out
 
     def tree_nonants(self):
         """z of the last solve per non-leaf node, in ``node_names`` order: [(node name, values)]."""

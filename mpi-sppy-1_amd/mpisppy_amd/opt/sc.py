@@ -117,9 +117,16 @@ class SchurComplement(SPOpt):
         e.fix_nonants(None)
         if self._tree:
             e.eft_init(*data[0], *data[1:7], self.tol, data[7])
+            zfix = self._held_z()
+            if zfix is not None:
+                e.eft_fix(zfix)
         else:
             e.ef_init(*data[:6], self.tol, data[6])
         self.is_qp = data[-1]
+
+    def _held_z(self):
+        """z entries to hold at values ([Ztot], NaN = free), or None (opt/ef.py fix_node_nonants)."""
+        return None
 
     def _run(self):
         """The iterations; True when the iterate passes the test."""

@@ -29,6 +29,11 @@ def node_idx(node_path, branching_factors):
     return _nodenum_before_stage(len(node_path), branching_factors) + stage_id
 
 
+def number_of_nodes(branching_factors):
+    """sputils.py:977-980: the index of the tree's last node (what the sample-tree seeds advance by)."""
+    return node_idx([bf - 1 for bf in branching_factors], list(branching_factors))
+
+
 def create_nodenames_from_branching_factors(BFS):
     stage_nodes = ["ROOT"]
     nodenames = ["ROOT"]

@@ -13,6 +13,16 @@ one-launch form costs, phase by phase, next to the same interval computed batch 
 
     python tools/mmw_ci.py [--batches 32] [--batch-size 2048] [--xhat-scens 30] [--ph-iters 50]
                            [--reps 200] [--no-loop] [--out FILE]
+
+``--model aircond --bf a,b,c`` runs the MULTISTAGE interval instead (EF_mstage) on
+sample trees with those branching factors: per batch G and s, the interior-point iterations of the
+free extensive form and of each stage's conditioned one, and the seconds spent in the free extensive
+form, the conditioned ones and the two evaluations.  Then, unless ``--no-loop``, the reference's walk
+on the first batch's sample tree -- one SampleSubtree per node -- for its time and the largest
+iteration count among the subtrees of each stage: what sharing one mu and one pair of step lengths
+over a stage's subtrees costs, and what solving a stage at once buys.
+
+    python tools/mmw_ci.py --model aircond --bf 4,3,2 [--batches 3] [--no-loop] [--out FILE]
 """
 import argparse
 import json
@@ -90,8 +100,86 @@ def moments_next_to_expectations(a, xhat, start):
     return res
 
 
+def aircond_interval(a):
+    """The multistage interval on aircond (module docstring)."""
+    import numpy as np
+    import torch
+    from mpisppy_amd.confidence_intervals import ciutils, sample_tree
+    from mpisppy_amd.examples import aircond
+    from mpisppy_amd.sputils import number_of_nodes
+    bfs = [int(v) for v in a.bf.split(",")]
+    S = int(np.prod(bfs))
+    cfg = {"branching_factors": bfs, "EF_mstage": True, "EF_solver_name": SOLVER, "device": "cuda:0"}
+    t0 = time.perf_counter()
+    xhat = ciutils.ef_xstar_solver(aircond, solver_name=SOLVER, device="cuda:0")(
+        aircond.scenario_names_creator(S), {"branching_factors": bfs, "start_seed": 0})
+    print(f"xhat_one {xhat} from the extensive form of a {bfs} tree at seed 0 ({time.perf_counter() - t0:.3f} s)", flush=True)
+    res = {"model": "aircond", "bf": bfs, "xhat_one": xhat.tolist(), "batches": []}
+    seed = S
+    for rnd, nb in (("warm-up", 1), ("timed", a.batches)):          # the first round loads the code objects
+        s0 = seed
+        for b in range(nb):
+            info = {}
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            try:
+                est = ciutils.gap_estimators({"ROOT": xhat}, aircond, solving_type="EF_mstage",
+                                             sample_options={"branching_factors": bfs, "seed": s0}, cfg=cfg, solver_name=SOLVER,
+                                             info=info)
+            except RuntimeError as err:                # (an extensive form short of its tolerance: say where it stopped)
+                print(f"[{rnd}] batch {b} (seed {s0}): no estimate: {err}", flush=True)
+                res.setdefault("failed", []).append({"seed": s0, "error": str(err)})
+                break
+            torch.cuda.synchronize()
+            wall = time.perf_counter() - t0
+            sec, it = info["seconds"], info["iterations"]
+            print(f"[{rnd}] batch {b} (seed {s0}): G {est['G']:.6f} s {est['s']:.6f}; iterations free {it['free']} conditioned "
+                  f"{it['conditioned']}; seconds {wall:.3f}: free {sec['free']:.4f} conditioned {sec['conditioned']:.4f} "
+                  f"(solves {['%.4f' % v for v in info['walk']['seconds']]}) evaluations {sec['evaluations']:.4f}", flush=True)
+            if rnd == "timed":
+                res["batches"].append({"seed": s0, "G": est["G"], "s": est["s"], "iterations": it, "seconds": sec,
+                                       "walk_seconds": info["walk"]["seconds"], "wall": wall})
+            s0 = est["seed"]
+    if not a.no_loop:
+        tree = sample_tree.SampleSubtree(aircond, [], None, 1, bfs, seed, cfg, SOLVER)
+        tree.run()
+        scens = dict(tree.ef.scenarios())
+        tree.close()
+        walk = {}
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        stopped = None
+        try:
+            sample_tree.walking_tree_xhats(aircond, scens, xhat, bfs, seed + number_of_nodes(bfs), cfg, solver_name=SOLVER,
+                                           info=walk, batched=False)
+        except RuntimeError as err:                    # (a subtree short of its tolerance ends the walk there)
+            stopped = str(err)
+        torch.cuda.synchronize()
+        loop = time.perf_counter() - t0
+        # the walk meets the nodes scenario by scenario: group its iteration counts by the node's stage
+        order = list(sample_tree.walk_seeds(scens, bfs, 0)[0])[:len(walk["iterations"])]
+        by_stage = {}
+        for nd, it in zip(order, walk["iterations"]):
+            by_stage.setdefault(nd.count("_") + 1, []).append(it)
+        worst = {t: max(v) for t, v in sorted(by_stage.items())}
+        res["one_at_a_time"] = {"seconds": loop, "subtrees": len(order), "max_iterations_by_stage": worst,
+                                "solve_seconds": float(np.sum(walk["seconds"])), "stopped": stopped}
+        if stopped:
+            print(f"one subtree at a time: the walk ended after {len(order)} subtrees: {stopped}", flush=True)
+        print(f"one subtree at a time: {len(order)} extensive forms in {loop:.3f} s; largest iteration count per stage {worst} "
+              f"(the stage's one conditioned solve: {res['batches'][0]['iterations']['conditioned'] if res['batches'] else 'none'})", flush=True)
+    line = json.dumps(res)
+    print(line, flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", choices=("farmer", "aircond"), default="farmer")
+    ap.add_argument("--bf", default="4,3,2", help="aircond: the sample trees' branching factors")
     ap.add_argument("--batches", type=int, default=32)
     ap.add_argument("--batch-size", type=int, default=2048)
     ap.add_argument("--xhat-scens", type=int, default=30)
@@ -100,6 +188,12 @@ def main():
     ap.add_argument("--no-loop", action="store_true", help="skip the batch-by-batch baseline")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.model == "aircond":
+        import torch
+        assert torch.cuda.is_available(), "tools/mmw_ci.py needs the GPU"
+        if a.batches == 32:
+            a.batches = 3
+        return aircond_interval(a)
     import numpy as np
     import torch
     from mpisppy_amd.confidence_intervals import ciutils
